@@ -30,9 +30,20 @@ Other workloads (`--workload`, one JSON line each; BASELINE.json configs):
   rf_module.cpp compiled from its sources, oracle/ref_driver.cpp ref_rx_streams).
 
 Prints ONE JSON line (rank 0).  `value` = complex IQ samples processed by all ranks
-per second (MS/s); `roofline` is for the step's dominant kernel (HIP events on the libsdr stream);
-`cpu_baseline` = the C restatement of the Python model (oracle/fm_oracle.c) on the
-host cores (rank 0, N=1).
+per second (MS/s); `roofline` is for the step's dominant kernel (HIP events on the libsdr stream).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what that line's headline
+needs: set up, warm up, time the N steps, print.  `--full` adds everything else, as one
+longer run: the measured stream ceilings beside the roofline (a copy and a read-only kernel),
+the CPU baselines of every workload (`cpu_baseline` = the C restatement of the Python model,
+oracle/fm_oracle.c, on the host cores, rank 0, N=1; the reference's own C++ where it was
+built) and, for mono, the other configurations appended to the line (c5 at 8 and 1 streams,
+u8, c3, c4, c4-span).  --no-cpu / --no-extras take single legs out of a --full run.
+
+`--dump-outputs DIR` (mono): after the timed steps, what the timed path left in device memory
+in its last step -- the arrays a caller of sdr_fe_mono_dev (audio), or of the split pair
+(demod, audio), receives -- is written as DIR/<name>.npy (float32).  The input is seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -65,8 +76,15 @@ def parse():
                     help="c5: 153 600-sample blocks of every stream processed per receiver call (device-resident "
                          "spans, time-parallel: FE and filters as one pass, PLLs as long calls); 1 = the per-block "
                          "receiver, one block of every stream per call")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the stream-kernel ceilings of the "
+                         "roofline, the CPU baselines and (mono) the other configurations appended to the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="mono: write the arrays the timed path produced in its last timed step to DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of them beyond 64 MB in all)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="mono: skip the c5 (8 and 1 streams) and u8 blocks appended to the headline line")
+                    help="mono --full: skip the c5 (8 and 1 streams), u8, c3 and c4 blocks appended to the headline "
+                         "line")
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default 50; c5: 256 blocks)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--settle-ms", type=float, default=250.0,
@@ -80,7 +98,7 @@ def parse():
     ap.add_argument("--iq", choices=["f32", "u8"], default="f32")
     ap.add_argument("--path", choices=["fused", "split"], default="fused",
                     help="fused: one fe_mono_kernel (demod stays on chip); split: FE kernel + FIR kernel")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--depth", type=int, default=2,
                     help="c3 / c4: sdr_rx_submit depth (blocks in flight; sdr_rx_set_depth)")
     ap.add_argument("--no-pipeline", action="store_true",
@@ -104,6 +122,12 @@ def parse():
     if a.steps is None:
         a.steps = ((256 if a.span == 1 else 10) if a.workload == "c5" else
                    (200 if a.workload in ("c3", "c4") else 50))
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs is not None and a.workload != "mono":
+        ap.error("--dump-outputs covers --workload mono (the headline path)")
+    a.cpu = a.full and not a.no_cpu
+    a.extras = a.full and not a.no_extras
     return a
 
 
@@ -231,6 +255,13 @@ def cpu_threads():
     return env if env > 0 else cpu_cores()[0]
 
 
+def synth_threads():
+    """Threads that build the headline's input (synth.fm_iq: the same samples at any count);
+    a 131 M-sample stream takes one core about half a minute.  Each holds a chunk's temporaries
+    (~0.3 GB), hence the cap."""
+    return min(8, cpu_threads())
+
+
 def copy_bandwidth(lib, handle, nbytes: int = 2 << 30, reps: int = 10, read_only: bool = False):
     """the achieved fraction beside a measured stream kernel on the same box --
     libsdr's 16-B-per-lane nontemporal copy (sdr_copy_bandwidth, GB/s counting read + write) or
@@ -257,6 +288,23 @@ def load_traffic(path, taps, blocks, kpath):
     except (OSError, ValueError):
         pass
     return None
+
+
+DUMP_BUDGET = 64_000_000       # bytes of --dump-outputs arrays in all
+
+
+def dump_outputs(path: str, arrays: dict, budget: int = DUMP_BUDGET):
+    """--dump-outputs: each array as path/<name>.npy (float32).  Whole while they fit the
+    budget together; beyond it every array keeps the same fraction of its elements, at sorted
+    positions drawn once from a fixed seed (the same positions in every run and build)."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.size * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32).ravel()
+        if total > budget:
+            keep = a.size * budget // total
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def split_range(n_total: int, ws: int, rank: int, halo: int, step: int = 50):
@@ -333,10 +381,10 @@ def main():
     if args.split_stream:
         # rank r: IQ [s0, s1) of the one stream plus the halo before s0 (no exchange)
         w0, s0, s1 = split_range(n_total, ws, rank, rtsdr.split_halo(len(rf_b), len(au_b)))
-        iq = rtsdr.synth.fm_iq(n_total, seed=0, dtype=dt)[2 * w0:2 * s1].copy()
+        iq = rtsdr.synth.fm_iq(n_total, seed=0, dtype=dt, threads=synth_threads())[2 * w0:2 * s1].copy()
         n = s1 - w0
     else:
-        iq = rtsdr.synth.fm_iq(n, seed=rank, dtype=dt)
+        iq = rtsdr.synth.fm_iq(n, seed=rank, dtype=dt, threads=synth_threads())
     M = (n + 9) // 10
     A = (M + 4) // 5
     dtype_code = _lib.SDR_IQ_U8 if args.iq == "u8" else _lib.SDR_IQ_F32
@@ -399,6 +447,12 @@ def main():
     ctx.synchronize()
     barrier(ws)
     elapsed = max_over_ranks(ws, time.perf_counter() - t0)
+    if args.dump_outputs is not None:
+        # what the last timed step left behind (nothing has run on the device since)
+        outs = {"audio": d_au.download(A)} if args.path == "fused" else \
+            {"demod": d_dm.download(M), "audio": d_au.download(A)}
+        dump_outputs(args.dump_outputs, {k + (f"_rank{rank}" if ws > 1 else ""): v for k, v in outs.items()})
+        del outs
     if per_step:
         stage_ms = [float(np.mean([tm.elapsed_ms(e[k], e[k + 1]) for e in ev])) for k in range(len(stages))]
     else:
@@ -463,7 +517,7 @@ def main():
             "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 4),
             "settle": {"untimed_steps": settle_steps, "min_ms": args.settle_ms},
         }
-    if rank == 0:
+    if rank == 0 and args.full:
         # the measured ceilings beside the kernel: a copy (read + write) and a read-only stream
         # (the FE reads 8 B per complex sample and writes 0.04 B).  frac_of_copy_kernel: against
         # the copy (rounds 1-2's field, comparable across rounds); frac_of_stream_ceiling:
@@ -475,16 +529,16 @@ def main():
         result["roofline"]["read_stream_gbs"] = rbw
         result["roofline"]["frac_of_copy_kernel"] = round(achieved / cbw, 4) if cbw else None
         result["roofline"]["frac_of_stream_ceiling"] = round(achieved / ceil, 4) if ceil else None
-    if ws == 1 and not args.no_cpu:
+    if ws == 1 and args.cpu:
         result["cpu_baseline"] = cpu_baseline(args, rf_b, au_b)
     elif rank == 0:
         result["cpu_baseline"] = None
     tm.close()
-    if not args.no_extras and not args.split_stream and args.iq == "f32" and args.path == "fused":
+    if args.extras and not args.split_stream and args.iq == "f32" and args.path == "fused":
         # the other configurations, measured in the same run (same box, same clock): C5 at its
         # per-GPU shapes (8 streams and 1 stream, >= 256 blocks per stream) and the u8 FE + mono
         del d_iq, d_dm, d_au
-        cpu = ws == 1 and not args.no_cpu and rank == 0
+        cpu = ws == 1 and args.cpu and rank == 0
         extras = {
             # (the standalone --workload c5 line's 10 timed spans after 10 warm-up spans: the
             # same measurement; r06 ran 5 after 2, ~8 % below the standalone line on one box)
@@ -650,7 +704,7 @@ def run_rx(args, ws, rank, local):
     _lib = import_module("real-time-software-defined-radio_amd._lib")
     ctx = _lib.Context(local)
     result = rx_measure(ctx, args.workload, args, rank, ws, args.steps, args.warmup,
-                        cpu=(ws == 1 and not args.no_cpu and rank == 0))
+                        cpu=(ws == 1 and args.cpu and rank == 0))
     if rank == 0:
         print(json.dumps(result), flush=True)
     if ws > 1:
@@ -1155,7 +1209,7 @@ def run_c5_span(args, ws, rank, local):
     _lib = import_module("real-time-software-defined-radio_amd._lib")
     ctx = _lib.Context(local)
     m = c5_measure(ctx, args.streams, args.span, args.steps, args.warmup, rank, ws,
-                   pipeline=not args.no_pipeline, cpu=(ws == 1 and not args.no_cpu and rank == 0), args=args)
+                   pipeline=not args.no_pipeline, cpu=(ws == 1 and args.cpu and rank == 0), args=args)
     if rank == 0:
         result = {"metric": "IQ MSamples/s through the multi-stream mono+stereo+RDS receiver (c5); "
                             "the dominant stage against its roofline",
@@ -1261,7 +1315,7 @@ def run_live(args, ws, rank, local):
     out["marginal_realtime_factor"] = round(g_marg / 2.4, 2)
     out["host_threads"] = 1
     visible, model = cpu_cores()
-    if os.path.exists(ref_bin) and not args.no_cpu:
+    if os.path.exists(ref_bin) and args.cpu:
         r_rows, r_marg = measure([ref_bin], [1, 2])
         out["cpu_baseline"] = {"value": r_rows[-1]["MS/s"], "unit": "MS/s", "cores": 4, "kind": "reference",
                                "cpu": model, "cores_visible": visible, "marginal_MS/s": r_marg,
@@ -1271,8 +1325,9 @@ def run_live(args, ws, rank, local):
                                          f"1x and 2x passes; {ref_provenance()}"}
     else:
         out["cpu_baseline"] = {"value": None, "kind": "reference",
-                               "sample": "not run: oracle/_ref/fm_radio absent (make -C oracle ref, where "
-                                         "/root/reference exists)" if not args.no_cpu else "skipped (--no-cpu)"}
+                               "sample": "not run: oracle/_ref/fm_radio absent (make -C oracle ref, where the "
+                                         "reference's sources are present)" if args.cpu else
+                                         "skipped (no --full, or --no-cpu)"}
     out["steps"] = args.live_repeat
     out["warmup"] = 0
     out["ms_per_step"] = round(g_rows[-1]["wall_s"] / args.live_repeat * 1e3, 3)

@@ -8,6 +8,8 @@ subcarrier, and +-1 RDS symbols at 2375 Bd on 57 kHz; frequency-modulated with
 """
 from __future__ import annotations
 
+from concurrent.futures import ThreadPoolExecutor
+
 import numpy as np
 
 FS = 2.4e6
@@ -48,8 +50,11 @@ def rds_symbols(nbits: int, seed: int = 0) -> np.ndarray:
 
 def fm_iq(n_complex: int, seed: int = 0, fs: float = FS, snr_db: float = 30.0, chunk: int = 1 << 22,
           dtype=np.float32, rds_groups: bool = False, rds_phase: float = 0.0, pilot_offset_hz: float = 0.0,
-          clock_ppm: float = 0.0) -> np.ndarray:
+          clock_ppm: float = 0.0, threads: int = 1) -> np.ndarray:
     """Interleaved float32 IQ of `n_complex` samples (generated in chunks to bound memory).
+    threads: chunks worked on at a time (numpy releases the GIL in its array loops); the
+    samples are the same bit for bit at any count -- only the noise draws and the phase
+    carried from chunk to chunk are sequential, and they stay so.
     rds_groups: the 57 kHz subcarrier carries coded RDS groups (rds_symbols) at carrier
     phase `rds_phase` instead of random symbols.
     pilot_offset_hz: the transmitter's pilot is 19 kHz + offset, and the 38 / 57 kHz
@@ -70,9 +75,9 @@ def fm_iq(n_complex: int, seed: int = 0, fs: float = FS, snr_db: float = 30.0, c
     noise_rng = np.random.default_rng(seed + 1_000_003)
     amp = 0.5
     sigma = amp / np.sqrt(2.0) * 10 ** (-snr_db / 20.0)
-    phase0 = 0.0
-    for start in range(0, n_complex, chunk):
-        n = min(chunk, n_complex - start)
+
+    def phase_steps(start, n):
+        """The FM phase over chunk [start, start + n), less the phase carried into it."""
         t = (start + np.arange(n, dtype=np.float64)) / fs_tx
         left = np.sin(2 * np.pi * 1e3 * t)
         right = 0.8 * np.sin(2 * np.pi * 2.5e3 * t)
@@ -80,11 +85,31 @@ def fm_iq(n_complex: int, seed: int = 0, fs: float = FS, snr_db: float = 30.0, c
         mpx = (0.45 * (left + right) / 2 + 0.1 * np.cos(2 * np.pi * fp * t)
                + 0.45 * (left - right) / 2 * np.cos(2 * np.pi * (2 * fp) * t)
                + 0.05 * rds * np.cos(2 * np.pi * (3 * fp) * t + rds_phase))
-        phi = phase0 + 2 * np.pi * 75e3 * np.cumsum(mpx) / fs_tx
-        phase0 = float(phi[-1])
-        noise = noise_rng.standard_normal((n, 2)) * sigma
+        return 2 * np.pi * 75e3 * np.cumsum(mpx) / fs_tx
+
+    def emit(start, n, phase0, steps, noise):
+        phi = phase0 + steps
         out[2 * start:2 * (start + n):2] = (amp * np.cos(phi) + noise[:, 0]).astype(np.float32)
         out[2 * start + 1:2 * (start + n):2] = (amp * np.sin(phi) + noise[:, 1]).astype(np.float32)
+
+    chunks = [(start, min(chunk, n_complex - start)) for start in range(0, n_complex, chunk)]
+    threads = max(1, min(int(threads), len(chunks)))
+    pool = ThreadPoolExecutor(threads) if threads > 1 else None
+    run = pool.map if pool else map
+    phase0 = 0.0
+    for g in range(0, len(chunks), threads):
+        group = chunks[g:g + threads]
+        steps = run(lambda c: phase_steps(*c), group)
+        # (drawn in chunk order, while the pool works)
+        noises = [noise_rng.standard_normal((n, 2)) * sigma for _, n in group]
+        steps = list(steps)
+        carried = []
+        for s in steps:
+            carried.append(phase0)
+            phase0 = float(phase0 + s[-1])
+        list(run(lambda a: emit(*a), [(*c, p, s, nz) for c, p, s, nz in zip(group, carried, steps, noises)]))
+    if pool:
+        pool.shutdown()
     if np.dtype(dtype) == np.uint8:
         return to_u8(out)
     return out

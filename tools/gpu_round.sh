@@ -8,7 +8,7 @@
 # steps:
 #   tests        the full -m gpu suite (+ smoke)                      -> pytest_gpu.txt, smoke.txt
 #   tests:<expr> the -m gpu tests matching -k <expr> (commas for spaces) -> pytest_<expr>.txt
-#   bench        python bench.py (the driver's default line)           -> bench_default.json
+#   bench        python bench.py --full (every configuration in one line) -> bench_default.json
 #   bench:<name>:<args...>   bench.py with args (commas for spaces)     -> bench_<name>.json
 #   prof:<name>:<args...>    rocprofv3 --kernel-trace --stats of it     -> prof_<name>/, prof_<name>.json
 #   pmc:<name>:<counters>:<args...>  one --pmc pass (counters comma-separated) -> pmc_<name>/
@@ -34,7 +34,7 @@ for step in "$@"; do
       timeout -k 10 500 python -u -m pytest tests -m gpu -v -s --timeout 200 --timeout-method thread -k "$k" \
         > "$O/pytest_$(echo "$k" | tr -c 'a-zA-Z0-9_\n' '_').txt" 2>&1 ;;
     bench)
-      timeout -k 10 400 python -u bench.py > "$O/bench_default.json" 2> "$O/bench_default.err" ;;
+      timeout -k 10 400 python -u bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err" ;;
     bench:*)
       IFS=: read -r _ name args <<< "$step"
       timeout -k 10 400 python -u bench.py $(sp "$args") > "$O/bench_$name.json" 2> "$O/bench_$name.err" ;;
