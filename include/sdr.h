@@ -111,6 +111,17 @@ int sdr_rf_frontend(sdr_ctx* ctx, const void* iq, int iq_dtype, int64_t n, const
 int sdr_lfilter_decim(sdr_ctx* ctx, const float* x, int64_t n, const double* b, int taps,
                       int decim, double* zi_inout, float* y);
 
+/* First-order IIR section: scipy.signal.lfilter([b0, b1], [1, a1], x, zi), i.e.
+ *   y[n] = b0 x[n] + z[n-1],  z[n] = b1 x[n] - a1 y[n],
+ * the state a single f64 in lfilter's zi / zf convention.  Samples f32 in and out, all
+ * arithmetic f64 (a parallel scan over the row, csrc/audio.hip).  The FM de-emphasis filter
+ * (design.deemphasis_coeffs: the bilinear transform of 1 / (1 + s tau), tau = 75 us or 50 us) is
+ * such a section; the reference has no de-emphasis, so there is no reference interface
+ * to name.  n >= 1, finite coefficients, |a1| <= 1; y must not overlap x.
+ * zi_inout: NULL = zero initial state and no state out. */
+int sdr_iir1(sdr_ctx* ctx, const float* x, int64_t n, const double* b /* [b0, b1] */, double a1,
+             double* zi_inout, float* y);
+
 /* lfilter with a fused input pre-op: PRE_SQUARE filters x*x
  * (model/fmRDSblock.py:161-164, src/filter.cpp:342-370), PRE_MIX filters
  * (x*mix)*gain (model/fmMonoBlock.py:155-160, model/fmRDSblock.py:173-182,
@@ -223,6 +234,28 @@ int sdr_pll_dev(sdr_ctx* ctx, const float* in, int64_t n, int64_t in_stride, int
 int sdr_stereo_combine_dev(sdr_ctx* ctx, const float* mono, const float* side, int64_t n,
                            float* left, float* right);
 
+/* sdr_iir1 on nstreams device rows (x_stride / y_stride >= n floats apart); zi, zf: nstreams
+ * doubles (zi NULL = zero state, zf NULL = no state out, zf may alias zi).  y must not overlap
+ * x.  Three launches for rows longer than one 2 048-sample tile (tile end states, one wave per
+ * row chaining them, apply), one otherwise; no workgroup waits for another inside a launch. */
+int sdr_iir1_dev(sdr_ctx* ctx, const float* x, int64_t n, int64_t x_stride, int nstreams,
+                 const double* b, double a1, const double* zi, double* zf, float* y, int64_t y_stride);
+
+/* Audio output stage: the rows left / right (nstreams rows each, `stride` floats apart; right
+ * NULL = mono, left on both PCM channels) through the first-order section b, a1 (b NULL = no
+ * filter), in any combination into the f32 rows left_out / right_out (same stride; must not
+ * overlap the inputs) and the interleaved int16 PCM rows L0 R0 L1 R1 .. (2 n values per stream,
+ * pcm_stride >= 2 n int16 elements apart).  state: [nstreams][2] doubles (L, R; in and out),
+ * required with a filter.  PCM rule, on the f32 sample x the stage wrote (or read, b NULL):
+ * v = x * 16384.0f in f32; NaN -> 0; v >= 32767 -> 32767; v <= -32768 -> -32768; otherwise
+ * truncation toward zero -- for finite in-range samples the conversion of
+ * src/fm_radio.cpp:286-302, and a defined result (saturation) where that one is undefined.
+ * SDR_EINVAL: n < 1, nstreams < 1, stride < n, pcm_stride < 2 n, non-finite coefficients,
+ * |a1| > 1, a filter without state, right_out without right, no output requested. */
+int sdr_audio_out_dev(sdr_ctx* ctx, const float* left, const float* right, int64_t n, int64_t stride,
+                      int nstreams, const double* b, double a1, double* state, float* left_out,
+                      float* right_out, int16_t* pcm, int64_t pcm_stride);
+
 /* ---- multi-stream block receiver ----------------------------------
  * The per-block loops of model/fmMonoBlock.py:80-173 (mono, stereo; intended L/R combiner)
  * and model/fmRDSblock.py:127-204 (RDS up to the RRC output) for `nstreams` independent
@@ -257,6 +290,7 @@ enum {
   SDR_RX_O_RDS_EXTRACT, SDR_RX_O_RDS_PRE_PLL, SDR_RX_O_RDS_NCO_I, SDR_RX_O_RDS_NCO_Q,
   SDR_RX_O_RDS_LPF_I, SDR_RX_O_RDS_LPF_Q, SDR_RX_O_RDS_RES_I, SDR_RX_O_RDS_RES_Q,
   SDR_RX_O_RDS_RRC_I, SDR_RX_O_RDS_RRC_Q,                           /* fmRDSblock.py:156-204 */
+  SDR_RX_O_AUDIO_DE, SDR_RX_O_LEFT_DE, SDR_RX_O_RIGHT_DE,           /* sdr_rx_set_deemph */
   SDR_RX_NOUTPUTS
 };
 int sdr_rx_create(sdr_ctx* ctx, int nstreams, int64_t block, int iq_dtype, int flags, sdr_rx** out);
@@ -265,6 +299,19 @@ int sdr_rx_set_filter(sdr_rx* rx, int which, const double* b, int taps);
 int sdr_rx_set_decim(sdr_rx* rx, int rf_decim, int audio_decim, int rds_up, int rds_down);
 int sdr_rx_set_pll(sdr_rx* rx, int which /* 0 stereo, 1 RDS */, double freq, double fs,
                    double nco_scale, double phase_adj, double norm_bw);
+/* Audio output stage (off by default; set before the first block; b NULL = off): the
+ * first-order section b = [b0, b1], a1 (sdr_iir1; FM de-emphasis) applied to the audio rows as
+ * one tail step on the context stream after the combiner.  SDR_RX_O_AUDIO_DE / _LEFT_DE /
+ * _RIGHT_DE are then ordinary output rows (A samples: the filtered SDR_RX_O_AUDIO / _LEFT /
+ * _RIGHT; the L / R rows with SDR_RX_STEREO only, and a stereo receiver filters its mono row
+ * only when SDR_RX_O_AUDIO_DE is kept, sdr_rx_set_keep), and sdr_rx_pcm gives the block's
+ * interleaved int16 PCM (sdr_audio_out_dev's rule; L / R with SDR_RX_STEREO, else the mono row on
+ * both channels; taken from the filtered rows): 2 A values per stream, *stride int16 apart.
+ * The f64 states (per stream and row) live in receiver memory, carry from block to block and
+ * are zeroed by sdr_rx_reset.  While the stage is off the three rows do not exist (SDR_EINVAL
+ * from every call that names them, and from sdr_rx_pcm), occupy no memory and cost no launch. */
+int sdr_rx_set_deemph(sdr_rx* rx, const double* b, double a1);
+int sdr_rx_pcm(sdr_rx* rx, int16_t** dev, int64_t* stride, int64_t* n);
 int sdr_rx_reset(sdr_rx* rx);                       /* all states back to the stream start */
 int sdr_rx_process_dev(sdr_rx* rx, const void* iq, int64_t iq_stride);   /* async, device IQ */
 int sdr_rx_process(sdr_rx* rx, const void* iq, int64_t iq_stride);       /* sync, host IQ */

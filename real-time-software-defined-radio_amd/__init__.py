@@ -10,7 +10,7 @@ Drop-in per-block functions with the reference's names and signatures
     my_filterImpulseResponse
 
 fused hot-path forms: lfilter_decim, rf_frontend_block, mono_block, resample,
-fm_mono_streams;
+fm_mono_streams; the audio output stage (FM de-emphasis, int16 PCM): iir1, deemphasis, audio_out;
 device-resident block pipelines: MonoBlockProcessor, StereoBlockProcessor,
 RdsBlockProcessor.  See DESIGN.md and INTEGRATION.md.
 """
@@ -21,6 +21,6 @@ from ._lib import (SDR_IQ_F32, SDR_IQ_U8, SDR_PRE_MIX, SDR_PRE_NONE, SDR_PRE_SQU
 from .blocks import MonoBlockProcessor, RdsBlockProcessor, RdsLinkLayer, Receiver, StereoBlockProcessor  # noqa: F401
 from .design import impulseResponseRootRaisedCosine, my_filterImpulseResponse  # noqa: F401
 from .dsp import (DFT, MonoState, estimatePSD, fm_mono_range, fm_mono_streams, split_halo, fmDemodArctan, fmPll, lfilter, lfilter_decim,  # noqa: F401
-                  mono_block, my_convoloution, resample, rf_frontend_block)
+                  audio_out, deemphasis, iir1, mono_block, my_convoloution, resample, rf_frontend_block)
 
 __version__ = "0.1.0"

@@ -25,7 +25,7 @@ RX_FILTERS = ("rf", "audio", "pilot", "stereo_bpf", "stereo_lpf", "rds_extract",
               "rds_anti", "rds_rrc")
 RX_OUTPUTS = ("demod", "audio", "bpf_recovery", "nco", "bpf_extraction", "stereo", "left", "right",
               "extract", "pre_pll", "nco_i", "nco_q", "lpf_i", "lpf_q", "resample_i", "resample_q",
-              "rrc_i", "rrc_q")
+              "rrc_i", "rrc_q", "audio_de", "left_de", "right_de")
 # stage C: the stereo mixer + LPF (and the RDS LPF rows when kept); "resample": the RDS mixers +
 # LPF + x19/80 resampler (the composite filter, csrc/rx.hip rx_cres_kernel)
 RX_STAGES = ("fe", "filters_of_demod", "rds_square", "pll", "mix_lpf", "resample", "rrc")
@@ -89,6 +89,9 @@ SIGNATURES = {
                            _i64]),
     "sdr_pll_stats": (_i32, [_vp, _vp, _i32]),
     "sdr_stereo_combine_dev": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "sdr_iir1": (_i32, [_vp, _fp, _i64, _dp, _f64, _dp, _fp]),
+    "sdr_iir1_dev": (_i32, [_vp, _vp, _i64, _i64, _i32, _dp, _f64, _vp, _vp, _vp, _i64]),
+    "sdr_audio_out_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _dp, _f64, _vp, _vp, _vp, _vp, _i64]),
     "sdr_psd": (_i32, [_vp, _dp, _i64, _i32, _f64, _dp]),
     "sdr_psd_dev": (_i32, [_vp, _vp, _i32, _i64, _i32, _f64, _vp]),
     "sdr_dft": (_i32, [_vp, _dp, _i64, _dp]),
@@ -98,6 +101,8 @@ SIGNATURES = {
     "sdr_rx_set_decim": (_i32, [_vp, _i32, _i32, _i32, _i32]),
     "sdr_rx_set_pll": (_i32, [_vp, _i32, _f64, _f64, _f64, _f64, _f64]),
     "sdr_rx_reset": (_i32, [_vp]),
+    "sdr_rx_set_deemph": (_i32, [_vp, _dp, _f64]),
+    "sdr_rx_pcm": (_i32, [_vp, _c.POINTER(_vp), _c.POINTER(_i64), _c.POINTER(_i64)]),
     "sdr_rx_process_dev": (_i32, [_vp, _vp, _i64]),
     "sdr_rx_process": (_i32, [_vp, _vp, _i64]),
     "sdr_rx_run": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),

@@ -47,12 +47,18 @@ class Receiver:
     the stereo channel and L/R (:113-173); rds=True the RDS chain to the RRC output
     (model/fmRDSblock.py:156-204).  Outputs (output(), process()'s return) are float32
     arrays of shape (nstreams, n); names as in the reference loops ("audio", "stereo",
-    "left", "right", "rrc_i", ...: _lib.RX_OUTPUTS)."""
+    "left", "right", "rrc_i", ...: _lib.RX_OUTPUTS).
+
+    deemphasis: an FM de-emphasis time constant in seconds (75e-6 or 50e-6; default None: off).
+    The receiver then also produces "audio_de" ("left_de", "right_de" with stereo=True) -- the
+    audio rows through design.deemphasis_coeffs(deemphasis, 240 kHz / audio_decim) on the device
+    (sdr_rx_set_deemph), state carried from block to block -- and pcm(), the block's interleaved
+    int16 samples; process()'s default outputs include the de-emphasised rows."""
 
     def __init__(self, nstreams: int, block_complex: int, *, mono: bool = True, stereo: bool = False,
                  rds: bool = False, iq_dtype=np.uint8, rf_coeff=None, audio_coeff=None, stereo_taps: int = 151,
                  rds_taps: int = 151, rf_decim: int = 10, audio_decim: int = 5, pipeline: bool = False,
-                 depth: int = 1, keep=None, ctx=None):
+                 depth: int = 1, keep=None, deemphasis=None, ctx=None):
         self.ctx = ctx if ctx is not None else _lib.get_context()
         self.lib = self.ctx.lib
         self.S, self.B = int(nstreams), int(block_complex)
@@ -88,6 +94,14 @@ class Receiver:
                   "sdr_rx_set_filter")
         check(self.lib.sdr_rx_set_decim(self.handle, int(rf_decim), int(audio_decim), design.RDS_UP,
                                         design.RDS_DOWN), "sdr_rx_set_decim")
+        self.deemphasis = None if deemphasis is None else float(deemphasis)
+        if self.deemphasis is not None:
+            if not flags & (SDR_RX_AUDIO | SDR_RX_STEREO):
+                raise ValueError("deemphasis needs an audio output (mono=True or stereo=True)")
+            b, a = design.deemphasis_coeffs(self.deemphasis, design.AUDIO_FS / audio_decim)
+            self.deemph_coeffs = (b, a)
+            check(self.lib.sdr_rx_set_deemph(self.handle, f64p(np.ascontiguousarray(b)), float(a[1])),
+                  "sdr_rx_set_deemph")
         if keep is not None:
             self.set_keep(keep)
         self.M = (self.B + rf_decim - 1) // rf_decim
@@ -105,6 +119,10 @@ class Receiver:
             return True
         if name == "audio":
             return bool(self.flags & (SDR_RX_AUDIO | SDR_RX_STEREO))
+        if name == "audio_de":
+            return self.deemphasis is not None and bool(self.flags & (SDR_RX_AUDIO | SDR_RX_STEREO))
+        if name in ("left_de", "right_de"):
+            return self.deemphasis is not None and bool(self.flags & SDR_RX_STEREO)
         if k <= RX_OUTPUTS.index("right"):
             return bool(self.flags & SDR_RX_STEREO)
         return bool(self.flags & SDR_RX_RDS)
@@ -118,7 +136,8 @@ class Receiver:
         plan = self._plans.get(key)
         if plan is None:                      # output names -> (which[], lengths, offsets), built once
             names = list(fetch) if fetch is not None else \
-                [n for n in ("audio", "left", "right", "rrc_i", "rrc_q") if n in self.outputs]
+                [n for n in ("audio", "left", "right", "rrc_i", "rrc_q", "audio_de", "left_de", "right_de")
+                 if n in self.outputs]
             which = (ctypes.c_int * len(names))(*[RX_OUTPUTS.index(n) for n in names])
             lengths = [self._length(n) for n in names]
             offs = [self.S * sum(lengths[:i]) for i in range(len(names))]
@@ -192,6 +211,16 @@ class Receiver:
               "sdr_rx_fetch")
         return out
 
+    def pcm(self) -> np.ndarray:
+        """The latest block's interleaved int16 PCM (sdr_rx_pcm), shape (nstreams, 2 A): L0 R0 L1 R1 ..
+        from "left_de" / "right_de" with stereo=True, else "audio_de" on both channels.  Needs
+        deemphasis."""
+        p, st, n = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int64()
+        check(self.lib.sdr_rx_pcm(self.handle, ctypes.byref(p), ctypes.byref(st), ctypes.byref(n)), "sdr_rx_pcm")
+        buf = np.empty((self.S, st.value), dtype=np.int16)
+        check(self.lib.sdr_memcpy_d2h(self.ctx.handle, buf.ctypes.data, p.value, buf.nbytes), "sdr_memcpy_d2h")
+        return np.ascontiguousarray(buf[:, :n.value])
+
     def state(self):
         """Carried states: (demod prev_phase [S], stereo PLL [S, 6], RDS PLL [S, 6])."""
         ph = np.empty(self.S)
@@ -254,9 +283,15 @@ class MonoBlockProcessor:
         return {k: v[0].astype(np.float64) for k, v in o.items()}
 
     def process(self, iq_block, return_demod: bool = False):
-        """audio_block (float64) for one block [+ fm_demod]."""
-        o = self._run(iq_block, ["audio", "demod"] if return_demod else ["audio"])
-        return (o["audio"], o["demod"]) if return_demod else o["audio"]
+        """audio_block (float64) for one block [+ fm_demod]; with deemphasis=tau, the
+        de-emphasised audio block."""
+        au = "audio" if self.rx.deemphasis is None else "audio_de"
+        o = self._run(iq_block, [au, "demod"] if return_demod else [au])
+        return (o[au], o["demod"]) if return_demod else o[au]
+
+    def pcm(self) -> np.ndarray:
+        """The latest block as interleaved int16 PCM (2 A values; needs deemphasis=tau)."""
+        return self.rx.pcm()[0]
 
     @property
     def phase(self) -> float:
@@ -274,6 +309,8 @@ class StereoBlockProcessor(MonoBlockProcessor):
 
     def process(self, iq_block, return_intermediates: bool = False):
         names = ["audio", "stereo", "left", "right"]
+        if self.rx.deemphasis is not None:
+            names += ["audio_de", "left_de", "right_de"]
         if return_intermediates:
             names += ["demod", "bpf_recovery", "nco", "bpf_extraction"]
         return self._run(iq_block, names)

@@ -136,6 +136,44 @@ int get_resp(sdr_ctx* c, const PllCfg& cfg, int64_t n, const double** out) {
   return SDR_OK;
 }
 
+int get_iir_tab(sdr_ctx* c, double a1, const double** out) {
+  for (const IirTab& t : c->iir)
+    if (t.a1 == a1) {
+      *out = t.dev;
+      return SDR_OK;
+    }
+  double h[SDR_IIR_THREADS + 1];
+  sdr_iir1_table(a1, h);
+  IirTab t;
+  t.a1 = a1;
+  HIP_TRY(hipMalloc(&t.dev, sizeof h));
+  HIP_TRY(hipMemcpy(t.dev, h, sizeof h, hipMemcpyHostToDevice));
+  c->iir.push_back(t);
+  *out = t.dev;
+  return SDR_OK;
+}
+
+int run_iir1(sdr_ctx* c, IirLaunch& a, const double* b, double a1, const char* what) {
+  a.filter = b != nullptr;
+  if (a.filter) {
+    if (!std::isfinite(b[0]) || !std::isfinite(b[1]) || !std::isfinite(a1))
+      return fail(SDR_EINVAL, "%s: non-finite coefficients", what);
+    if (std::fabs(a1) > 1.0) return fail(SDR_EINVAL, "%s: |a1| = %g > 1 (unstable section)", what, std::fabs(a1));
+    a.b0 = b[0];
+    a.b1 = b[1];
+    a.a1 = a1;
+    TRY(get_iir_tab(c, a1, &a.tab));
+    const int64_t nt = sdr_iir1_tiles(a.n);
+    if (nt > 1) {
+      const size_t cells = (size_t)a.nstreams * a.nch * (size_t)nt;
+      TRY(scratch(c, S_IIR, sizeof(double) * 2 * cells, (void**)&a.agg));
+      a.carry = a.agg + cells;
+    }
+  }
+  HIP_TRY(sdr_launch_iir1(a, c->stream));
+  return SDR_OK;
+}
+
 }  // namespace sdrint
 
 namespace {
@@ -248,6 +286,7 @@ void sdr_destroy(sdr_ctx* c) {
   for (int s = 0; s < S_NSLOT; ++s) if (c->slot[s]) (void)hipFree(c->slot[s]);
   for (TapSet& t : c->taps) { (void)hipFree(t.dev_f32); (void)hipFree(t.dev_f64); (void)hipFree(t.dev_afr); }
   for (RespTable& t : c->resp) (void)hipFree(t.dev);
+  for (IirTab& t : c->iir) (void)hipFree(t.dev);
   if (c->pll_stats) (void)hipFree(c->pll_stats);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
@@ -639,6 +678,62 @@ int sdr_stereo_combine_dev(sdr_ctx* c, const float* mono, const float* side, int
   return SDR_OK;
 }
 
+int sdr_iir1_dev(sdr_ctx* c, const float* x, int64_t n, int64_t x_stride, int nstreams, const double* b,
+                 double a1, const double* zi, double* zf, float* y, int64_t y_stride) {
+  CHECK_CTX(c);
+  if (n < 1 || nstreams < 1 || nstreams > 65535) return fail(SDR_EINVAL, "sdr_iir1_dev: n %lld, nstreams %d", (long long)n, nstreams);
+  if (x == nullptr || y == nullptr || b == nullptr) return fail(SDR_EINVAL, "sdr_iir1_dev: NULL buffer");
+  if (x_stride < n || y_stride < n)
+    return fail(SDR_EINVAL, "sdr_iir1_dev: stride (%lld, %lld) shorter than the row (%lld)", (long long)x_stride,
+                (long long)y_stride, (long long)n);
+  TRY(set_dev(c));
+  IirLaunch a{};
+  a.x[0] = x;
+  a.x_stride = x_stride;
+  a.nch = 1;
+  a.nstreams = nstreams;
+  a.n = n;
+  a.zi = zi;
+  a.zf = zf;
+  a.st_stride = 1;
+  a.y[0] = y;
+  a.y_stride = y_stride;
+  return run_iir1(c, a, b, a1, "sdr_iir1_dev");
+}
+
+int sdr_audio_out_dev(sdr_ctx* c, const float* left, const float* right, int64_t n, int64_t stride, int nstreams,
+                      const double* b, double a1, double* state, float* left_out, float* right_out, int16_t* pcm,
+                      int64_t pcm_stride) {
+  CHECK_CTX(c);
+  if (n < 1 || nstreams < 1 || nstreams > 65535)
+    return fail(SDR_EINVAL, "sdr_audio_out_dev: n %lld, nstreams %d", (long long)n, nstreams);
+  if (left == nullptr) return fail(SDR_EINVAL, "sdr_audio_out_dev: left is NULL");
+  if (stride < n) return fail(SDR_EINVAL, "sdr_audio_out_dev: stride %lld shorter than the row (%lld)", (long long)stride, (long long)n);
+  if (pcm != nullptr && pcm_stride < 2 * n)
+    return fail(SDR_EINVAL, "sdr_audio_out_dev: pcm_stride %lld < 2 n (%lld)", (long long)pcm_stride, (long long)(2 * n));
+  if (b != nullptr && state == nullptr) return fail(SDR_EINVAL, "sdr_audio_out_dev: a filter needs its state");
+  if (left_out == nullptr && right_out == nullptr && pcm == nullptr)
+    return fail(SDR_EINVAL, "sdr_audio_out_dev: no output requested");
+  if (right == nullptr && right_out != nullptr) return fail(SDR_EINVAL, "sdr_audio_out_dev: right_out without right");
+  TRY(set_dev(c));
+  IirLaunch a{};
+  a.x[0] = left;
+  a.x[1] = right;
+  a.x_stride = stride;
+  a.nch = right != nullptr ? 2 : 1;
+  a.nstreams = nstreams;
+  a.n = n;
+  a.zi = b != nullptr ? state : nullptr;
+  a.zf = b != nullptr ? state : nullptr;
+  a.st_stride = 2;
+  a.y[0] = left_out;
+  a.y[1] = right_out;
+  a.y_stride = stride;
+  a.pcm = pcm;
+  a.pcm_stride = pcm_stride;
+  return run_iir1(c, a, b, a1, "sdr_audio_out_dev");
+}
+
 // ================================================================================
 // Host-buffer drop-in API (synchronous)
 // ================================================================================
@@ -717,6 +812,25 @@ int sdr_lfilter(sdr_ctx* c, const float* x, const float* mix, float gain, int pr
                   zi_inout ? dz + Z + 1 : nullptr, dy, M));
   TRY(d2h(c, y, dy, sizeof(float) * M));
   if (zi_inout) TRY(d2h(c, zi_inout, dz + Z + 1, sizeof(double) * Z));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return SDR_OK;
+}
+
+int sdr_iir1(sdr_ctx* c, const float* x, int64_t n, const double* b, double a1, double* zi_inout, float* y) {
+  CHECK_CTX(c);
+  if (n < 1) return fail(SDR_EINVAL, "sdr_iir1: n %lld < 1", (long long)n);
+  if (x == nullptr || y == nullptr || b == nullptr) return fail(SDR_EINVAL, "sdr_iir1: NULL buffer");
+  TRY(set_dev(c));
+  float *dx, *dy;
+  double* dz;
+  TRY(scratch(c, S_IN, sizeof(float) * (size_t)n, (void**)&dx));
+  TRY(scratch(c, S_OUT, sizeof(float) * (size_t)n, (void**)&dy));
+  TRY(scratch(c, S_STATE, sizeof(double), (void**)&dz));
+  TRY(h2d(c, dx, x, sizeof(float) * n));
+  if (zi_inout) TRY(h2d(c, dz, zi_inout, sizeof(double)));
+  TRY(sdr_iir1_dev(c, dx, n, n, 1, b, a1, zi_inout ? dz : nullptr, zi_inout ? dz : nullptr, dy, n));
+  TRY(d2h(c, y, dy, sizeof(float) * n));
+  if (zi_inout) TRY(d2h(c, zi_inout, dz, sizeof(double)));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return SDR_OK;
 }

@@ -35,6 +35,10 @@
 // 151*24 = 3624-tap sinc design divides 0/0 at its tap 1812 (src/filter.cpp:29-33) and
 // writes NaN audio, i.e. silence (:290-293).  Per block it writes floor(15360*24/125) =
 // 2 949 samples, as the reference does (src/filter.cpp:264).
+// --deemph 50|75: FM de-emphasis with that time constant in us (75: Americas, Korea; 50:
+// elsewhere; default off -- the reference has none) and the int16 conversion on the
+// device: the final L / R rows go through libsdr's audio output stage (the receiver's own in mode
+// 0, sdr_audio_out_dev in mode 1) and only the interleaved int16 PCM comes back.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -121,7 +125,7 @@ struct Dev {
 
 int main(int argc, char** argv) {
   bool mono = false, print_taps = false, rds = false, resync = false;
-  int rf_taps = 151, mode = 0;
+  int rf_taps = 151, mode = 0, deemph = 0;
   long long max_blocks = -1;
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--mono")) mono = true;
@@ -131,9 +135,11 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--rf-taps") && i + 1 < argc) rf_taps = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--blocks") && i + 1 < argc) max_blocks = std::atoll(argv[++i]);
     else if (!std::strcmp(argv[i], "--mode") && i + 1 < argc) mode = std::atoi(argv[++i]);
+    else if (!std::strcmp(argv[i], "--deemph") && i + 1 < argc &&
+             (!std::strcmp(argv[i + 1], "50") || !std::strcmp(argv[i + 1], "75"))) deemph = std::atoi(argv[++i]);
     else {
       std::fprintf(stderr, "usage: fm_radio_gpu [--mode 0|1] [--mono] [--rds [--resync]] [--rf-taps N] [--blocks N] "
-                           "[--print-taps] < iq_u8 > pcm_s16le_stereo\n");
+                           "[--deemph 50|75] [--print-taps] < iq_u8 > pcm_s16le_stereo\n");
       return 2;
     }
   }
@@ -176,6 +182,15 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
+  // de-emphasis at the 48 kHz audio rate: the prewarped bilinear transform of 1 / (1 + s tau)
+  // (design.deemphasis_coeffs)
+  double de_b[2] = {0.0, 0.0}, de_a1 = 0.0;
+  if (deemph) {
+    const double fs = 48e3, tau = deemph == 75 ? 75e-6 : 50e-6;
+    const double wca = 2.0 * fs * std::tan(1.0 / (2.0 * fs * tau)), kk = wca / (2.0 * fs);
+    de_b[0] = de_b[1] = kk / (1.0 + kk);
+    de_a1 = -(1.0 - kk) / (1.0 + kk);
+  }
   sdr_ctx* c = nullptr;
   const char* dev_env = std::getenv("SDR_DEVICE");
   ck(sdr_create(dev_env ? std::atoi(dev_env) : 0, &c), "sdr_create");
@@ -213,6 +228,13 @@ int main(int argc, char** argv) {
     const double init[6] = {0.0, 0.0, 1.0, 0.0, 1.0, 0.0};            // model/fmMonoBlock.py:76
     hk(hipMemcpyAsync(pll_st, init, sizeof init, hipMemcpyHostToDevice, st), "H2D");
   }
+  // --deemph, mode 1: the stage's states (L, R) and its PCM row
+  double* de_st = nullptr;
+  int16_t* d_pcm = nullptr;
+  if (deemph && mode == 1) {
+    de_st = static_cast<double*>(d.alloc(8 * 2));
+    d_pcm = static_cast<int16_t*>(d.alloc(4 * A + 16));
+  }
   hk(hipStreamSynchronize(st), "hipStreamSynchronize");
 
   // two-slot pinned ring
@@ -227,6 +249,10 @@ int main(int argc, char** argv) {
   std::vector<int16_t> pcm(2 * A);
   auto emit = [&](int slot) {          // block in h_out[slot] -> int16 L/R (src/fm_radio.cpp:286-302)
     hk(hipEventSynchronize(done[slot]), "hipEventSynchronize");
+    if (deemph) {                      // the device's PCM (2 A int16 in the slot)
+      if (std::fwrite(h_out[slot], sizeof(int16_t), 2 * A, stdout) != (size_t)(2 * A)) std::exit(0);
+      return;
+    }
     const float* L = h_out[slot];
     const float* R = h_out[slot] + A;
     for (int64_t i = 0; i < A; ++i) {
@@ -258,6 +284,7 @@ int main(int argc, char** argv) {
         {SDR_RX_F_STEREO_LPF, &ste_b}, {SDR_RX_F_RDS_EXTRACT, &rex_b}, {SDR_RX_F_RDS_SQUARE, &rsq_b},
         {SDR_RX_F_RDS_LPF, &rlp_b}, {SDR_RX_F_RDS_ANTI, &ran_b}, {SDR_RX_F_RDS_RRC, &rrc_b}};
     for (const auto& f : taps) ck(sdr_rx_set_filter(rx, f.first, f.second->data(), (int)f.second->size()), "taps");
+    if (deemph) ck(sdr_rx_set_deemph(rx, de_b, de_a1), "sdr_rx_set_deemph");
     float* p;
     int64_t stride, n;
     ck(sdr_rx_output(rx, mono ? SDR_RX_O_AUDIO : SDR_RX_O_LEFT, &p, &stride, &n), "output");
@@ -334,8 +361,21 @@ int main(int argc, char** argv) {
       finish(pending);
       pending = -1;
     }
-    hk(hipMemcpyAsync(h_out[slot], out_l, 4 * A, hipMemcpyDeviceToHost, st), "D2H");
-    hk(hipMemcpyAsync(h_out[slot] + A, out_r, 4 * A, hipMemcpyDeviceToHost, st), "D2H");
+    if (deemph) {
+      const int16_t* pcm_d = d_pcm;
+      if (mode == 0) {
+        int16_t* p;
+        ck(sdr_rx_pcm(rx, &p, nullptr, nullptr), "sdr_rx_pcm");
+        pcm_d = p;
+      } else {
+        ck(sdr_audio_out_dev(c, out_l, stereo1 ? out_r : nullptr, A, A, 1, de_b, de_a1, de_st, nullptr, nullptr, d_pcm,
+                             2 * A), "audio output stage");
+      }
+      hk(hipMemcpyAsync(h_out[slot], pcm_d, 4 * A, hipMemcpyDeviceToHost, st), "D2H");
+    } else {
+      hk(hipMemcpyAsync(h_out[slot], out_l, 4 * A, hipMemcpyDeviceToHost, st), "D2H");
+      hk(hipMemcpyAsync(h_out[slot] + A, out_r, 4 * A, hipMemcpyDeviceToHost, st), "D2H");
+    }
     if (rds) hk(hipMemcpyAsync(h_rrc[slot], o_rrc, 4 * nrrc, hipMemcpyDeviceToHost, st), "D2H");
     hk(hipEventRecord(done[slot], st), "hipEventRecord");
     pending = slot;

@@ -1921,6 +1921,15 @@ struct sdr_rx {
   uint64_t keep_now = ~0ull;           // this call's (sdr_rx_submit: what it was asked for)
   bool made[SDR_RX_NOUTPUTS] = {};     // what the latest block materialised
   float* ctaps = nullptr;              // the composite RDS taps (rx_cres_kernel), device; null: two-stage path
+  // sdr_rx_set_deemph: the audio output stage (audio.hip) after the combiner, on the context stream
+  bool de_on = false;
+  double de_b[2] = {}, de_a1 = 0.0;
+  void* de_mem = nullptr;              // the states, then the PCM rows of every row set
+  double* de_state = nullptr;          // [S][2]: left (mono without SDR_RX_STEREO), right
+  double* de_mono = nullptr;           // [S]: the mono row of a stereo receiver
+  int16_t* pcms[3] = {};               // interleaved L R rows, pcm_stride int16 apart, per row set
+  int16_t* pcm = nullptr;              // the latest block's
+  int64_t pcm_stride = 0;
 };
 
 namespace {
@@ -1937,6 +1946,8 @@ bool need_out(const sdr_rx* r, int o) {
     case SDR_RX_O_AUDIO: return au;
     case SDR_RX_O_BPF_RECOVERY: case SDR_RX_O_STEREO_NCO: case SDR_RX_O_BPF_EXTRACTION:
     case SDR_RX_O_STEREO: case SDR_RX_O_LEFT: case SDR_RX_O_RIGHT: return st;
+    case SDR_RX_O_AUDIO_DE: return au && r->de_on;
+    case SDR_RX_O_LEFT_DE: case SDR_RX_O_RIGHT_DE: return st && r->de_on;
     default: return rd;
   }
 }
@@ -1987,6 +1998,7 @@ int rx_finalize(sdr_rx* r) {
     int64_t n, st;
     switch (o) {
       case SDR_RX_O_AUDIO: case SDR_RX_O_STEREO: case SDR_RX_O_LEFT: case SDR_RX_O_RIGHT:
+      case SDR_RX_O_AUDIO_DE: case SDR_RX_O_LEFT_DE: case SDR_RX_O_RIGHT_DE:
         n = r->A; st = as; break;
       case SDR_RX_O_STEREO_NCO: case SDR_RX_O_RDS_NCO_I: case SDR_RX_O_RDS_NCO_Q:
         n = M + 1; st = ms; break;
@@ -2049,6 +2061,15 @@ int rx_finalize(sdr_rx* r) {
       HIP_TRY(hipMemcpy(r->ctaps, ct.data(), sizeof(float) * ct.size(), hipMemcpyHostToDevice));
     }
   }
+  if (r->de_on) {
+    r->pcm_stride = round_up(2 * r->A, 64);
+    const size_t sb = sizeof(double) * (size_t)(3 * S2 + 2), pb = sizeof(int16_t) * (size_t)(S * r->pcm_stride);
+    HIP_TRY(hipMalloc(&r->de_mem, sb + nsets * pb));
+    r->de_state = static_cast<double*>(r->de_mem);
+    r->de_mono = r->de_state + 2 * S2;
+    for (int q = 0; q < nsets; ++q) r->pcms[q] = reinterpret_cast<int16_t*>(static_cast<char*>(r->de_mem) + sb + q * pb);
+    r->pcm = r->pcms[0];
+  }
   r->ready = true;
   return sdr_rx_reset(r);
 }
@@ -2088,6 +2109,7 @@ void sdr_rx_destroy(sdr_rx* r) {
   }
   if (r->mem) (void)hipFree(r->mem);
   if (r->ctaps) (void)hipFree(r->ctaps);
+  if (r->de_mem) (void)hipFree(r->de_mem);
   if (r->pin_in) (void)hipHostFree(r->pin_in);
   if (r->pin_out) (void)hipHostFree(r->pin_out);
   for (hipEvent_t e : r->ev)
@@ -2149,12 +2171,41 @@ int sdr_rx_reset(sdr_rx* r) {
   }
   HIP_TRY(hipMemcpyAsync(r->pll_state[0], ps.data(), sizeof(double) * ps.size(), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(r->pll_state[1], ps.data(), sizeof(double) * ps.size(), hipMemcpyHostToDevice, st));
+  if (r->de_state) HIP_TRY(hipMemsetAsync(r->de_state, 0, sizeof(double) * (size_t)(3 * round_up(r->S, 2)), st));
   HIP_TRY(hipStreamSynchronize(st));
   r->parity = 0;
   r->blocks = 0;
   r->last_fs = nullptr;
   r->host_done = -1;
   std::memcpy(r->out, r->outs[0], sizeof r->out);
+  r->pcm = r->pcms[0];
+  return SDR_OK;
+}
+
+int sdr_rx_set_deemph(sdr_rx* r, const double* b, double a1) {
+  if (r == nullptr) return fail(SDR_EINVAL, "sdr_rx is NULL");
+  if (r->ready) return fail(SDR_EINVAL, "sdr_rx_set_deemph: the receiver has processed a block");
+  if (b == nullptr) {
+    r->de_on = false;
+    return SDR_OK;
+  }
+  if (!(r->flags & (SDR_RX_AUDIO | SDR_RX_STEREO))) return fail(SDR_EINVAL, "sdr_rx_set_deemph: flags 0x%x produce no audio", r->flags);
+  if (!std::isfinite(b[0]) || !std::isfinite(b[1]) || !std::isfinite(a1)) return fail(SDR_EINVAL, "sdr_rx_set_deemph: non-finite coefficients");
+  if (std::fabs(a1) > 1.0) return fail(SDR_EINVAL, "sdr_rx_set_deemph: |a1| = %g > 1", std::fabs(a1));
+  r->de_b[0] = b[0];
+  r->de_b[1] = b[1];
+  r->de_a1 = a1;
+  r->de_on = true;
+  return SDR_OK;
+}
+
+int sdr_rx_pcm(sdr_rx* r, int16_t** dev, int64_t* stride, int64_t* n) {
+  if (r == nullptr) return fail(SDR_EINVAL, "sdr_rx is NULL");
+  if (!r->de_on) return fail(SDR_EINVAL, "sdr_rx_pcm: the audio output stage is off (sdr_rx_set_deemph)");
+  if (!r->ready) TRY(rx_finalize(r));
+  if (dev) *dev = r->pcm;
+  if (stride) *stride = r->pcm_stride;
+  if (n) *n = 2 * r->A;
   return SDR_OK;
 }
 
@@ -2490,11 +2541,24 @@ int sdr_rx_process_dev(sdr_rx* r, const void* iq, int64_t iq_stride) {
   } else {
     HIP_TRY(mark(1 + SDR_RX_ST_D, st));
   }
+  // the audio output stage (audio.hip): de-emphasis of L / R (mono without SDR_RX_STEREO) into
+  // their _DE rows and the interleaved PCM, and of a stereo receiver's mono row when it is kept
+  const bool de_mono = r->de_on && stx && kept(SDR_RX_O_AUDIO_DE);
+  if (r->de_on) {
+    TRY(sdr_audio_out_dev(c, o[stx ? SDR_RX_O_LEFT : SDR_RX_O_AUDIO], stx ? o[SDR_RX_O_RIGHT] : nullptr, r->A, as, S,
+                          r->de_b, r->de_a1, r->de_state, o[stx ? SDR_RX_O_LEFT_DE : SDR_RX_O_AUDIO_DE],
+                          stx ? o[SDR_RX_O_RIGHT_DE] : nullptr, r->pcms[q], r->pcm_stride));
+    if (de_mono)
+      TRY(sdr_iir1_dev(c, o[SDR_RX_O_AUDIO], r->A, as, S, r->de_b, r->de_a1, r->de_mono, r->de_mono,
+                       o[SDR_RX_O_AUDIO_DE], as));
+    r->pcm = r->pcms[q];
+  }
   for (int oo = 0; oo < SDR_RX_NOUTPUTS; ++oo) {
     const bool nco_o = oo == SDR_RX_O_STEREO_NCO || oo == SDR_RX_O_RDS_NCO_I || oo == SDR_RX_O_RDS_NCO_Q;
     const bool lpf_o = oo == SDR_RX_O_RDS_LPF_I || oo == SDR_RX_O_RDS_LPF_Q;
     const bool pin_o = oo == SDR_RX_O_BPF_RECOVERY || oo == SDR_RX_O_RDS_PRE_PLL;      // (codes: when kept)
-    r->made[oo] = need_out(r, oo) && (!nco_o || nco_rows) && (!lpf_o || lpf_rows) && (!pin_o || !codes || kept(oo));
+    r->made[oo] = need_out(r, oo) && (!nco_o || nco_rows) && (!lpf_o || lpf_rows) && (!pin_o || !codes || kept(oo)) &&
+                  (oo != SDR_RX_O_AUDIO_DE || !stx || de_mono);
   }
   HIP_TRY(mark(1 + SDR_RX_ST_E, st));
   if (r->pipe) HIP_TRY(hipEventRecord(r->ev_back[q], st));
@@ -2524,7 +2588,8 @@ int grow_pinned(sdr_rx* r, void** p, size_t* cap, size_t bytes) {
 // outputs a stage kernel stores (and can store a host copy of); the demod (FE kernel) and
 // the NCOs (PLL) come back by copy
 bool stage_output(int o) {
-  return o != SDR_RX_O_DEMOD && o != SDR_RX_O_STEREO_NCO && o != SDR_RX_O_RDS_NCO_I && o != SDR_RX_O_RDS_NCO_Q;
+  return o != SDR_RX_O_DEMOD && o != SDR_RX_O_STEREO_NCO && o != SDR_RX_O_RDS_NCO_I && o != SDR_RX_O_RDS_NCO_Q &&
+         o != SDR_RX_O_AUDIO_DE && o != SDR_RX_O_LEFT_DE && o != SDR_RX_O_RIGHT_DE;   // (the audio output stage)
 }
 
 // Deliver the block in flight: wait for it, copy its rows out of pinned memory.

@@ -16,7 +16,7 @@ namespace sdrint {
 // scratch slots owned by a context (grown on demand, never shrunk)
 enum Slot {
   S_IN, S_IN2, S_OUT, S_OUT2, S_OUT3, S_OUT4, S_STATE, S_STATE2, S_MISC, S_THETA, S_PHI, S_WRAP,
-  S_PSD, S_PLLW,
+  S_PSD, S_PLLW, S_IIR,
   S_NSLOT
 };
 
@@ -36,6 +36,12 @@ struct RespTable {
   double* dev = nullptr;
 };
 
+// a first-order section's pole-power table on the device (sdr_iir1_table), per a1
+struct IirTab {
+  double a1 = 0.0;
+  double* dev = nullptr;
+};
+
 // the calling thread's last error message; returns `code`
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
@@ -52,6 +58,8 @@ struct sdr_ctx {
   std::list<sdrint::TapSet> taps;
   // PLL response tables of the long calls made on the context (a few loops; never evicted)
   std::list<sdrint::RespTable> resp;
+  // pole-power tables of the first-order sections run on the context (a few; never evicted)
+  std::list<sdrint::IirTab> iir;
   // PLL solve counters (SDR_PLL_NSTATS, device; sdr_pll_stats): every PLL launch of the
   // context and of its receivers adds to them
   unsigned long long* pll_stats = nullptr;
@@ -73,6 +81,13 @@ int get_resp(sdr_ctx* c, const PllCfg& cfg, int64_t n, const double** out);
 inline const float* resp32_of(const double* resp, int64_t pb) {
   return resp != nullptr ? reinterpret_cast<const float*>(resp + 2 * (pb + 5)) : nullptr;
 }
+
+// the device pole-power table of a first-order section with denominator [1, a1] (cached per context)
+int get_iir_tab(sdr_ctx* c, double a1, const double** out);
+// validates the section (finite b, a1, |a1| <= 1), fills a.b0 / b1 / a1 / filter / tab and the
+// tile scratch (context slot S_IIR) and launches the stage on the context stream; b == NULL: no
+// filter.  `what` names the entry point in error messages.
+int run_iir1(sdr_ctx* c, IirLaunch& a, const double* b, double a1, const char* what);
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

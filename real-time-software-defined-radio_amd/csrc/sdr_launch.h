@@ -140,3 +140,28 @@ hipError_t sdr_launch_pll_prep(const PllJobs& jobs, hipStream_t st);
 hipError_t sdr_launch_pll_loop(const PllJobs& jobs, hipStream_t st);
 hipError_t sdr_launch_pll_nco(const PllJobs& jobs, hipStream_t st);
 hipError_t sdr_launch_pll_jobs(const PllJobs& jobs, hipStream_t st);
+
+// First-order IIR section + PCM stage (audio.hip): per stream s and channel ch < nch, the row
+// x[ch] + s * x_stride of n samples through lfilter([b0, b1], [1, a1]) with the f64 state
+// zi / zf [s * st_stride + ch] (zf may alias zi), into y[ch] (nullable) and, as int16, into
+// pcm[s * pcm_stride + 2 i + ch] (nullable; nch == 1 writes the row to both channels).
+// filter == 0: the rows go to y / pcm unfiltered.  A workgroup of SDR_IIR_THREADS lanes covers a
+// tile of SDR_IIR_TILE samples, SDR_IIR_ITEMS per lane.
+#define SDR_IIR_THREADS 256
+#define SDR_IIR_ITEMS 8
+#define SDR_IIR_TILE (SDR_IIR_THREADS * SDR_IIR_ITEMS)
+struct IirLaunch {
+  const float* x[2]; int64_t x_stride; int nch; int nstreams; int64_t n;
+  int filter; double b0, b1, a1;
+  const double* tab;           // device: sdr_iir1_table(a1), SDR_IIR_THREADS + 1 doubles
+  const double* zi; double* zf; int st_stride;
+  float* y[2]; int64_t y_stride; int16_t* pcm; int64_t pcm_stride;
+  double* agg; double* carry;  // rows of more than one tile: nstreams * nch * sdr_iir1_tiles(n) doubles each
+  // set by the launcher
+  int64_t ntiles, K; double q[6]; int vec_x, vec_y, vec_pcm;
+};
+// tab[k] = (-a1)^(SDR_IIR_ITEMS k), k = 0 .. SDR_IIR_THREADS (host, f64 pow)
+void sdr_iir1_table(double a1, double* tab);
+int64_t sdr_iir1_tiles(int64_t n);
+// reduce -> carry -> apply (rows of one tile, or filter == 0: apply alone)
+hipError_t sdr_launch_iir1(const IirLaunch& a, hipStream_t st);

@@ -43,6 +43,19 @@ PILOT_FREQ = 19e3
 STEREO_PLL_SCALE = 2.0
 
 
+def deemphasis_coeffs(tau: float = 75e-6, fs: float = 48e3):
+    """(b, a) of the FM de-emphasis filter: the bilinear transform of 1 / (1 + s tau), prewarped
+    so that the -3 dB point stays at 1 / (2 pi tau) -- scipy.signal.bilinear([wca], [1, wca], fs)
+    with wca = 2 fs tan(1 / (2 fs tau)).  tau: 75e-6 (Americas, Korea) or 50e-6 (elsewhere).
+    The reference has no de-emphasis; this is the filter broadcast receivers apply to undo the
+    transmitter's pre-emphasis."""
+    if not (tau > 0 and fs > 0):
+        raise ValueError("tau and fs must be positive")
+    wca = 2.0 * fs * math.tan(1.0 / (2.0 * fs * tau))
+    k = wca / (2.0 * fs)
+    return np.array([k / (1.0 + k), k / (1.0 + k)]), np.array([1.0, -(1.0 - k) / (1.0 + k)])
+
+
 def firwin_lpf(taps: int, fc: float, fs: float) -> np.ndarray:
     """signal.firwin(taps, fc/(fs/2), window='hann') as at model/fmMonoBlock.py:43."""
     return signal.firwin(taps, fc / (fs / 2), window=("hann"))

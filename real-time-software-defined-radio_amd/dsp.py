@@ -14,6 +14,9 @@ per block.  Same names, argument meaning, return shapes and error behaviour:
 plus the fused forms the hot path is built from:
 
     lfilter_decim(b, x, zi, decim)             lfilter(...)[::decim] in one kernel
+    iir1(b, a, x, zi)                          lfilter for a first-order section (a = [a0, a1])
+    deemphasis(x, tau, fs, zi)                 FM de-emphasis (design.deemphasis_coeffs + iir1)
+    audio_out(left, right, ...)                de-emphasis + interleaved int16 PCM of audio rows
     rf_frontend_block(iq, rf_coeff, zi_i, zi_q, prev_phase, rf_decim=10)
     mono_block(iq, rf_coeff, audio_coeff, state)
     resample(x, b, zi, up, down)               model/fmRDSblock.py:184-199
@@ -100,6 +103,101 @@ def lfilter(b, a, x, zi=None, ctx=None):
     """scipy.signal.lfilter for FIR b (a scalar), as called at model/fmMonoBlock.py:86-91."""
     b = _taps(b, a)
     return lfilter_decim(b, x, zi, 1, ctx=ctx)
+
+
+def _section(b, a):
+    """([b0, b1], a1) of a first-order section b, a (one or two coefficients each), normalised
+    by a[0] as scipy does."""
+    b = np.atleast_1d(np.asarray(b))
+    a = np.atleast_1d(np.asarray(a))
+    if b.ndim != 1 or a.ndim != 1:
+        raise ValueError("object of too small depth for desired array")
+    if np.iscomplexobj(b) or np.iscomplexobj(a):
+        raise NotImplementedError(f"input type '{np.result_type(b, a)}' not supported")
+    if not (1 <= len(b) <= 2 and 1 <= len(a) <= 2):
+        raise NotImplementedError("iir1 takes a first-order section: at most two coefficients in b and in a")
+    a0 = float(a[0])
+    if a0 == 0.0:
+        raise ValueError("a[0] must be non-zero")
+    bb = np.zeros(2)
+    bb[:len(b)] = np.asarray(b, dtype=np.float64) / a0
+    return bb, (float(a[1]) / a0 if len(a) == 2 else 0.0)
+
+
+def iir1(b, a, x, zi=None, ctx=None):
+    """scipy.signal.lfilter(b, a, x, zi=zi) for a first-order section (len(b), len(a) <= 2;
+    |a[1] / a[0]| <= 1) on the GPU: f32 samples, f64 arithmetic and state (sdr_iir1, a parallel
+    scan).  Returns (y, zf) when zi (shape (1,)) is given, else y, as lfilter_decim does."""
+    bb, a1 = _section(b, a)
+    x = c_f32(_check_x(x))
+    zi = _check_zi(zi, 2)
+    c = _ctx(ctx)
+    n = x.shape[0]
+    y = np.empty(n, dtype=np.float32)
+    zf = zi.copy() if zi is not None else None
+    if n > 0:
+        check(c.lib.sdr_iir1(c.handle, f32p(x), n, f64p(bb), a1, f64p(zf), f32p(y)), "sdr_iir1")
+    y = y.astype(np.float64)
+    return (y, zf) if zi is not None else y
+
+
+def deemphasis(x, tau: float = 75e-6, fs: float = 48e3, zi=None, ctx=None):
+    """FM de-emphasis of an audio stream sampled at fs: iir1 with design.deemphasis_coeffs(tau,
+    fs).  (y, zf) when zi is given, else y."""
+    from . import design
+    b, a = design.deemphasis_coeffs(tau, fs)
+    return iir1(b, a, x, zi, ctx=ctx)
+
+
+def audio_out(left, right=None, *, b=None, a=None, state=None, rows=True, pcm=True, ctx=None):
+    """The audio output stage on (nstreams, n) rows (sdr_audio_out_dev): left / right (right
+    None: mono on both channels) through the first-order section b, a (None: no filter), returned
+    as a dict of the f32 rows ("left", "right"; rows=True) and the interleaved int16 PCM
+    ("pcm", shape (nstreams, 2 n), L0 R0 L1 R1 ..; pcm=True): x * 16384 saturated to int16, NaN -> 0,
+    else truncated toward zero.  state: (nstreams, 2) f64 (L, R), updated in place; zeros when
+    None."""
+    c = _ctx(ctx)
+    L = np.ascontiguousarray(np.atleast_2d(left), dtype=np.float32)
+    R = None if right is None else np.ascontiguousarray(np.atleast_2d(right), dtype=np.float32)
+    if R is not None and R.shape != L.shape:
+        raise ValueError("left and right must have the same shape")
+    S, n = L.shape
+    bb, a1 = (None, 0.0) if b is None else _section(b, 1.0 if a is None else a)
+    if bb is not None and state is None:
+        state = np.zeros((S, 2))
+    if state is not None and (state.shape != (S, 2) or state.dtype != np.float64 or not state.flags.c_contiguous):
+        raise ValueError(f"state must be a C-contiguous float64 array of shape ({S}, 2)")
+    D = _lib.DeviceBuffer
+    bufs = []
+
+    def dev(arr=None, nbytes=0):
+        buf = D.from_array(c, arr) if arr is not None else D(c, max(nbytes, 16))
+        bufs.append(buf)
+        return buf
+    try:
+        dl, dr = dev(L), dev(R) if R is not None else None
+        dst = dev(state) if bb is not None else None
+        ol = dev(nbytes=4 * S * n) if rows else None
+        orr = dev(nbytes=4 * S * n) if rows and R is not None else None
+        dp = dev(nbytes=4 * S * n) if pcm else None
+        check(c.lib.sdr_audio_out_dev(c.handle, dl.ptr, dr.ptr if dr else None, n, n, S, f64p(bb), a1,
+                                      dst.ptr if dst else None, ol.ptr if ol else None, orr.ptr if orr else None,
+                                      dp.ptr if dp else None, 2 * n), "sdr_audio_out_dev")
+        out = {}
+        if ol:
+            out["left"] = ol.download(S * n).reshape(S, n)
+        if orr:
+            out["right"] = orr.download(S * n).reshape(S, n)
+        if dp:
+            out["pcm"] = dp.download(2 * S * n, dtype=np.int16).reshape(S, 2 * n)
+        if dst:
+            state[...] = dst.download(2 * S, dtype=np.float64).reshape(S, 2)
+        if not out:
+            c.synchronize()
+        return out
+    finally:
+        for buf in bufs:
+            buf.free()
 
 
 def fmDemodArctan(I, Q, prev_phase=0.0, ctx=None):
