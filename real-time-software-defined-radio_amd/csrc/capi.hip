@@ -91,6 +91,8 @@ int get_taps(sdr_ctx* c, const double* b, int T, const TapSet** out, int max_T) 
   std::vector<float> f(T);
   for (int k = 0; k < T; ++k) f[k] = (float)b[k];
   for (int k = 0; k < std::min(T, SDR_MAX_TAPS); ++k) t.h.h[k] = f[k];
+  t.sym = T <= SDR_MAX_TAPS;
+  for (int k = 0; k < T / 2 && t.sym; ++k) t.sym = f[k] == f[T - 1 - k];
   const int cap = std::max(T, SDR_MAX_TAPS);
   std::vector<float> fr(cap + T + 4, 0.f);          // forward | pad, 0, reversed, 0, 0
   std::copy(f.begin(), f.end(), fr.begin());
@@ -110,30 +112,53 @@ int get_taps(sdr_ctx* c, const double* b, int T, const TapSet** out, int max_T) 
   return SDR_OK;
 }
 
+namespace {
+constexpr size_t kMaxPllTables = 16;   // per list: a receiver's two loops, and room to retune them
+
+// The table of (cfg, pb) in `cache`, uploaded on a miss: `build` fills the doubles, and with_f32
+// appends the same values as floats.  A hit moves to the back; an overflow evicts the front once
+// nothing on the device can still read it (a receiver's PLL launches run on streams of its own).
+template <class Build>
+int pll_table(std::list<PllTable>& cache, const PllCfg& cfg, int64_t pb, bool with_f32, Build build, const double** out) {
+  for (auto it = cache.begin(); it != cache.end(); ++it)
+    if (it->kp == cfg.kp && it->ki == cfg.ki && it->pb == pb) {
+      cache.splice(cache.end(), cache, it);
+      *out = it->dev;
+      return SDR_OK;
+    }
+  if (cache.size() >= kMaxPllTables) {
+    HIP_TRY(hipDeviceSynchronize());
+    (void)hipFree(cache.front().dev);
+    cache.pop_front();
+  }
+  std::vector<double> h;
+  build(&h);
+  const std::vector<float> hf(h.begin(), with_f32 ? h.end() : h.begin());
+  PllTable t{cfg.kp, cfg.ki, pb, nullptr};
+  hipError_t e = hipMalloc(&t.dev, sizeof(double) * h.size() + sizeof(float) * hf.size());
+  if (e == hipSuccess) e = hipMemcpy(t.dev, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess && with_f32) e = hipMemcpy(t.dev + h.size(), hf.data(), sizeof(float) * hf.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(t.dev);
+    return fail(SDR_EHIP, "PLL table upload: %s", hipGetErrorString(e));
+  }
+  cache.push_back(t);
+  *out = t.dev;
+  return SDR_OK;
+}
+}  // namespace
+
 int get_resp(sdr_ctx* c, const PllCfg& cfg, int64_t n, const double** out) {
   *out = nullptr;
   int64_t pb;
   int nb;
   if (!sdr_pll_long_geom(n, &pb, &nb)) return SDR_OK;
-  for (const RespTable& t : c->resp)
-    if (t.kp == cfg.kp && t.ki == cfg.ki && t.pb == pb) {
-      *out = t.dev;
-      return SDR_OK;
-    }
-  std::vector<double> h;
-  sdr_pll_resp_table(cfg, n, &h);
-  RespTable t;
-  t.kp = cfg.kp;
-  t.ki = cfg.ki;
-  t.pb = pb;
-  // the f64 rows, then the same rows in f32 (NcoSrc::resp32, sdr_resp32)
-  std::vector<float> hf(h.begin(), h.end());
-  HIP_TRY(hipMalloc(&t.dev, sizeof(double) * h.size() + sizeof(float) * hf.size()));
-  HIP_TRY(hipMemcpy(t.dev, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(t.dev + h.size(), hf.data(), sizeof(float) * hf.size(), hipMemcpyHostToDevice));
-  c->resp.push_back(t);
-  *out = t.dev;
-  return SDR_OK;
+  // the f64 rows, then the same rows in f32 (NcoSrc::resp32, resp32_of)
+  return pll_table(c->resp, cfg, pb, true, [&](std::vector<double>* h) { sdr_pll_resp_table(cfg, n, h); }, out);
+}
+
+int get_qtab(sdr_ctx* c, const PllCfg& cfg, const double** out) {
+  return pll_table(c->qtab, cfg, 0, false, [&](std::vector<double>* h) { qtab_host(cfg, h); }, out);
 }
 
 int get_iir_tab(sdr_ctx* c, double a1, const double** out) {
@@ -285,7 +310,8 @@ void sdr_destroy(sdr_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (int s = 0; s < S_NSLOT; ++s) if (c->slot[s]) (void)hipFree(c->slot[s]);
   for (TapSet& t : c->taps) { (void)hipFree(t.dev_f32); (void)hipFree(t.dev_f64); (void)hipFree(t.dev_afr); }
-  for (RespTable& t : c->resp) (void)hipFree(t.dev);
+  for (PllTable& t : c->resp) (void)hipFree(t.dev);
+  for (PllTable& t : c->qtab) (void)hipFree(t.dev);
   for (IirTab& t : c->iir) (void)hipFree(t.dev);
   if (c->pll_stats) (void)hipFree(c->pll_stats);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -650,6 +676,7 @@ int sdr_pll_dev(sdr_ctx* c, const float* in, int64_t n, int64_t in_stride, int n
   P.stats = c->pll_stats;
   P.nco_rows = 1;                                   // fmPll's outputs are the NCO rows
   TRY(get_resp(c, P.j[0].cfg, n, &P.j[0].resp));
+  TRY(get_qtab(c, P.j[0].cfg, &P.j[0].qtab));
   const int64_t wb = sdr_pll_work_bytes(1, nstreams, n);    // long calls: pseudo-block records
   if (wb > 0) TRY(scratch(c, S_PLLW, (size_t)wb, &P.work));
   HIP_TRY(sdr_launch_pll_jobs(P, c->stream));

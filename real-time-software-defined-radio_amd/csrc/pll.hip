@@ -38,7 +38,6 @@
 #include <stdlib.h>
 
 #include <cmath>
-#include <mutex>
 
 #include "sdr_launch.h"
 #include "sdr_nco.h"
@@ -533,12 +532,6 @@ struct Mat2 { double a, b, c, d; };
 __device__ __forceinline__ Mat2 mmul(const Mat2& x, const Mat2& y) {
   return {x.a * y.a + x.b * y.c, x.a * y.b + x.b * y.d, x.c * y.a + x.d * y.c, x.c * y.b + x.d * y.d};
 }
-__device__ __forceinline__ Mat2 mpow2(Mat2 x, int e) {
-  Mat2 r{1.0, 0.0, 0.0, 1.0};
-  for (; e > 0; e >>= 1, x = mmul(x, x))
-    if (e & 1) r = mmul(r, x);
-  return r;
-}
 
 // SPEC_T threads (chunks) per recurrence: 256 (one wave per SIMD) up to 10 240 samples, 512
 // beyond (the warm-up is the same length either way; 512 halves the chunks, and a second
@@ -666,17 +659,6 @@ __device__ __forceinline__ bool spec_body(const PllJobs& P, const int bid, const
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
     lrow = reinterpret_cast<Th32Line*>(((uintptr_t)hi << 32) | lo);
   }
-#ifdef SDR_PLL_SPEC_PROF    // phase timers (diagnostic builds only, tools/build_dbg.sh)
-#ifndef SDR_PLL_SPEC_PROF_TID
-#define SDR_PLL_SPEC_PROF_TID 0   // the thread whose timers print (-D...=448: wave 7, a storing wave)
-#endif
-  long long tp[16];
-  int ntp = 0;
-  tp[ntp++] = clock64();
-#define SPEC_TP() do { if (ntp < 16) tp[ntp++] = clock64(); } while (0)
-#else
-#define SPEC_TP() do {} while (0)
-#endif
   const double* st_call = J.state + (int64_t)s * 6;
   double* st = LONG ? (from_call ? J.state + (int64_t)s * 6 : status == LB_NEED_G ? LB->g : LB->x)
                     : J.state + (int64_t)s * 6;
@@ -786,7 +768,6 @@ __device__ __forceinline__ bool spec_body(const PllJobs& P, const int bid, const
   }
   if (tid < 2 * QT_N) qt2[tid] = qv;
   __syncthreads();
-  SPEC_TP();
   // r04b: a wave whose chunks are all full runs the step loops without a per-step "inside the
   // chunk" predicate (its selects and compares were a fifth of the check loop's VALU); the wave
   // holding the last, partial chunk (and the unused ones) keeps them.  wfast: also every chunk
@@ -841,7 +822,6 @@ __device__ __forceinline__ bool spec_body(const PllJobs& P, const int bid, const
       if (wfull) corr(std::true_type{});
       else corr(std::false_type{});
     }
-    SPEC_TP();
     yb[tid] = d2v{(double)z.x, -(double)z.y};
     __syncthreads();
     // the 5-chunk sums around this chunk and around the one before it: each thread forms both
@@ -882,7 +862,6 @@ __device__ __forceinline__ bool spec_body(const PllJobs& P, const int bid, const
     yb[tid].x = D;                               // D_j
     __syncthreads();
   }
-  SPEC_TP();
   const double p1 = x1s[0], v1 = x1s[1];
   // 1. guess.  With every m_k fixed at the floor the pass itself takes, a pass over a chunk IS
   // the loop's linear form x' = A x + u_k, so the chunk's response from zero state -- what the
@@ -952,7 +931,6 @@ __device__ __forceinline__ bool spec_body(const PllJobs& P, const int bid, const
         }
       }
     }
-    SPEC_TP();
     __syncthreads();                             // yb (D_j) read before tb reuses its space
     xs_p = p;                                    // the guess's chunk start (after the warm-up)
     xs_v = V;
@@ -986,12 +964,10 @@ __device__ __forceinline__ bool spec_body(const PllJobs& P, const int bid, const
     };
     if (wfull) guess(std::true_type{});
     else guess(std::false_type{});
-    SPEC_TP();
     xe_p = p;                                    // ... and its end
     xe_v = V;
   }
   if (__syncthreads_or(bad)) return false;       // a 0 / NaN input (the general form's case)
-  SPEC_TP();
   // Q = A^L's powers from the job's table (qtab_host, built once per loop on the host, staged in
   // LDS with the sign codes): Q^(2^i) for the scan's offsets, Q^(lane+1) and Q^tid = Q^(64 w)
   // Q^lane for the chunk starts -- r06: instead of thread 0 forming them (A^L step by step, then
@@ -1016,7 +992,6 @@ __device__ __forceinline__ bool spec_body(const PllJobs& P, const int bid, const
         lrow[(rb + kk) / TH32_LINE] = ln;
       }
     }
-    SPEC_TP();                                   // (the phase timers: the compact rows' lines)
     // 2. solve: the chunk's response from zero state to the current integers, from the last
     // pass over it (the guess in round 0, the previous check after): z_j = x_end - Q x_start
     double zp, zv;
@@ -1032,7 +1007,6 @@ __device__ __forceinline__ bool spec_body(const PllJobs& P, const int bid, const
     const Mat2 Ql = QT[lane + 1], Qj = mmul(QT[65 + wv], QT[lane]);   // Q^(lane+1), Q^tid
     double yp = tid < TE ? zp : 0.0, yv = tid < TE ? zv : 0.0;
     double cp = 0.0, cv = 0.0;                   // Y at the end of the previous wave
-    SPEC_TP();                                   // (the phase timers: z and the Q powers)
     {
       // (r06: DPP moves -- offsets 1, 2, 4, 8 within rows of 16, a lane past its row's start
       // adding Q^o x the lane o before it; then rows 1 / 3 take Q^((lane & 15) + 1) x lane 15 of
@@ -1049,9 +1023,7 @@ __device__ __forceinline__ bool spec_body(const PllJobs& P, const int bid, const
       step(QT[(lane & 15) + 1], dpp_f64<0x142, 0xa>(0.0, yp), dpp_f64<0x142, 0xa>(0.0, yv));
       step(QT[(lane & 31) + 1], dpp_f64<0x143, 0xc>(0.0, yp), dpp_f64<0x143, 0xc>(0.0, yv));
       if (lane == 63) wsum[wv] = d2v{yp, yv};
-      SPEC_TP();                                 // (the phase timers: the scan's shuffles / its barrier)
       __syncthreads();
-      SPEC_TP();
       // the carry, Y at the previous wave's end = sum over the waves before of Q^(64 (wv-1-i))
       // x their totals (QT[65 + w] = Q^(64 w)): independent products, not a chain of wv
       // dependent steps (r06: the last wave waited out seven)
@@ -1066,14 +1038,12 @@ __device__ __forceinline__ bool spec_body(const PllJobs& P, const int bid, const
       }
       yp = yp + (Ql.a * cp + Ql.b * cv);
       yv = yv + (Ql.c * cp + Ql.d * cv);
-      SPEC_TP();
     }
     // Y_{j-1}: the previous lane's (lane 0: the carry); the check's barrier orders these wsum
     // reads before the next round's writes
     double vp = dpp_f64<0x138>(cp, yp), vv = dpp_f64<0x138>(cv, yv);   // (wave_shr:1; lane 0 keeps the carry)
     vp = vp + (Qj.a * p1 + Qj.b * v1);           // + Q^j x_1
     vv = vv + (Qj.c * p1 + Qj.d * v1);
-    SPEC_TP();
     // 3. check: the true step from y_j.  The phases go out as the theta row on every round (a
     // later round or the sequential kernel overwrites a failed one): each batch of SB steps
     // of the wave's 64 chunks turns through tw so that a store covers 8 chunks x SB steps
@@ -1179,7 +1149,6 @@ __device__ __forceinline__ bool spec_body(const PllJobs& P, const int bid, const
       else if (wpre) check(std::true_type{}, std::true_type{}, std::false_type{});
       else check(std::false_type{}, std::false_type{}, std::false_type{});
     }
-    SPEC_TP();
     float mth = fminf(__uint_as_float(mlo), 1.f - __uint_as_float(mhi));
     xe_p = p;
     xe_v = V;
@@ -1189,15 +1158,6 @@ __device__ __forceinline__ bool spec_body(const PllJobs& P, const int bid, const
       if (lane == 0) mg[wv] = mth;
     }
     const int nmiss = __syncthreads_count(miss);
-    SPEC_TP();
-#ifdef SDR_PLL_SPEC_PROF
-    if (tid == SDR_PLL_SPEC_PROF_TID && nmiss == 0 && (bid == 0 || (bid % 479) == 3))
-      printf("spec_prof blk %d L %d: stage %lld corrloop %lld corrscan %lld warm %lld guessloop %lld guesssync %lld "
-             "lines %lld zq %lld wshfl %lld wbar %lld xscan %lld ystart %lld checkloop %lld checksync %lld (%d marks)\n",
-             bid, L, tp[1] - tp[0], tp[2] - tp[1], tp[3] - tp[2], tp[4] - tp[3], tp[5] - tp[4], tp[6] - tp[5],
-             tp[7] - tp[6], tp[8] - tp[7], tp[9] - tp[8], tp[10] - tp[9], tp[11] - tp[10], tp[12] - tp[11],
-             tp[13] - tp[12], tp[14] - tp[13], ntp);
-#endif
     if (nmiss == 0) {
       if constexpr (LONG) {
         // a pre-roll's state at the block start (after step pre - 1): the thread whose chunk
@@ -1965,13 +1925,12 @@ M2 mpow(M2 x, int64_t e) {
   return r;
 }
 // c1, c2: the largest |phase deviation| over the steps after a unit start error in phaseEst
-// (c1) or in the integrator (c2), iterated until the loop has damped it (cached per loop)
+// (c1) or in the integrator (c2), iterated until the loop has damped it (a pure function of the
+// loop, remembered per thread for its first 16 loops: two doubles each, no lock, nothing to free)
 struct Bounds { double kp, ki, c1, c2; };
 void loop_bounds(const PllCfg& c, double* c1, double* c2) {
-  static std::mutex mu;
-  static Bounds cache[16];
-  static int ncache = 0;
-  std::lock_guard<std::mutex> g(mu);
+  thread_local Bounds cache[16];
+  thread_local int ncache = 0;
   for (int i = 0; i < ncache; ++i)
     if (cache[i].kp == c.kp && cache[i].ki == c.ki) { *c1 = cache[i].c1; *c2 = cache[i].c2; return; }
   const M2 A = loop_matrix(c);
@@ -2079,6 +2038,8 @@ HM2 hmul(const HM2& x, const HM2& y) {
 #pragma clang fp contract(off)
   return {x.a * y.a + x.b * y.c, x.a * y.b + x.b * y.d, x.c * y.a + x.d * y.c, x.c * y.b + x.d * y.d};
 }
+}  // namespace
+
 void qtab_host(const PllCfg& cfg, std::vector<double>* out) {
 #pragma clang fp contract(off)
   const double kA = k2Pi * cfg.ki, kC = k2Pi * (cfg.kp + cfg.ki);
@@ -2106,35 +2067,6 @@ void qtab_host(const PllCfg& cfg, std::vector<double>* out) {
     for (int w = 0; w < 8; ++w) t[65 + w] = pw(64 * w);
   }
 }
-// device copies, per (device, kp, ki), for the life of the process (QT_NL x QT_N x 32 B = 12 KB each)
-struct QTab { int dev; double kp, ki; double* d; };
-hipError_t qtab_get(const PllCfg& cfg, const double** out) {
-  static std::mutex mu;
-  static std::vector<QTab> cache;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  std::lock_guard<std::mutex> g(mu);
-  for (const QTab& t : cache)
-    if (t.dev == dev && t.kp == cfg.kp && t.ki == cfg.ki) { *out = t.d; return hipSuccess; }
-  std::vector<double> h;
-  qtab_host(cfg, &h);
-  QTab t{dev, cfg.kp, cfg.ki, nullptr};
-  e = hipMalloc(&t.d, sizeof(double) * h.size());
-  if (e == hipSuccess) e = hipMemcpy(t.d, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return e;
-  cache.push_back(t);
-  *out = t.d;
-  return hipSuccess;
-}
-hipError_t qtab_fill(PllJobs& L) {
-  for (int q = 0; q < L.njobs; ++q) {
-    const hipError_t e = qtab_get(L.j[q].cfg, &L.j[q].qtab);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-}  // namespace
 
 hipError_t sdr_launch_pll_prep(const PllJobs& P, hipStream_t st) {
   bool vec;
@@ -2156,12 +2088,13 @@ hipError_t sdr_launch_pll_loop(const PllJobs& P, hipStream_t st) {
   hipError_t e = pll_check(P, &vec);
   if (e != hipSuccess) return e;
   PllJobs L = P;
+  for (int q = 0; q < P.njobs; ++q)                  // the solve's matrix powers are the caller's to bring
+    if ((pll_long(P) || spec_only(P)) && P.j[q].qtab == nullptr) return hipErrorInvalidValue;
   if (pll_long(P)) {
     // long call: every pseudo-block solved (from warm-up guesses), then the chain with its repairs
     L.qform = 0;
     e = long_setup(L);
     if (e == hipSuccess) e = th32_check(L);
-    if (e == hipSuccess) e = qtab_fill(L);
     if (e != hipSuccess) return e;
     const int R = L.njobs * L.nstreams;
     hipLaunchKernelGGL((pll_spec_kernel<512, true>), dim3((unsigned)(R * L.lg.nb)), dim3(512), 0, st, L);
@@ -2175,8 +2108,6 @@ hipError_t sdr_launch_pll_loop(const PllJobs& P, hipStream_t st) {
     L.lpw = 0;
     L.qform = 0;
     L.nco_fused = P.nco_rows ? 1 : 0;
-    e = qtab_fill(L);
-    if (e != hipSuccess) return e;
     const dim3 g((unsigned)(L.njobs * L.nstreams));
     if (L.n > SPEC_N256) hipLaunchKernelGGL((pll_spec_kernel<512, false>), g, dim3(512), 0, st, L);
     else hipLaunchKernelGGL((pll_spec_kernel<256, false>), g, dim3(256), 0, st, L);

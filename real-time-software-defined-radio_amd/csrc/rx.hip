@@ -1177,40 +1177,40 @@ int64_t tile_outputs(const StageJob& j, int key) {
   static_assert(PairShape<151, 2>::TO == FirShape<151, 1, 4>::TO && PairShape<151, 8>::TO == FirShape<151, 1>::TO &&
                 PairShape<101, 2>::TO == FirShape<101, 1, 4>::TO && PairShape<101, 8>::TO == FirShape<101, 1>::TO,
                 "pair tiles and the mixers' fir tiles cover the same outputs");
-  if (j.kind == JK_FIR && key == 151 && j.D == 1 && j.small) return FirShape<151, 1, 4>::TO;
-  if (j.kind == JK_FIR && key == 101 && j.D == 1 && j.small) return FirShape<101, 1, 4>::TO;
-  if (j.kind == JK_FIR && key == 151 && j.D == 1) return FirShape<151, 1>::TO;
-  if (j.kind == JK_FIR && key == 151 && j.D == 5) return FirShape<151, 5>::TO;
-  if (j.kind == JK_FIR && key == 101 && j.D == 1) return FirShape<101, 1>::TO;
-  if (j.kind == JK_FIR && key == 101 && j.D == 5) return FirShape<101, 5>::TO;
-  return RX_TO;
+  if (j.kind != JK_FIR || key == 0 || (j.D != 1 && j.D != 5)) return RX_TO;
+  if (j.D == 5) return key == 151 ? FirShape<151, 5>::TO : FirShape<101, 5>::TO;
+  if (j.small) return key == 151 ? FirShape<151, 1, 4>::TO : FirShape<101, 1, 4>::TO;
+  return key == 151 ? FirShape<151, 1>::TO : FirShape<101, 1>::TO;
 }
 
-// Launch the jobs of one stage, one launch per tap-count class.
-hipError_t launch_stage(std::vector<StageJob> jobs, int S, hipStream_t st, const FeState* fe = nullptr) {
-  auto cls = [](const StageJob& j) { return (j.kind == JK_FIR && (j.T == 101 || j.T == 151)) ? j.T : 0; };
-  // matrix-core FIR launches first: D = 1 filters of 101 / 151 taps on 16-B aligned rows of at
-  // least MM_MIN_WIN windows per stream (spans; per-block calls keep the VALU tiles' finer
-  // grain) -- decided per job from its length alone, so a stream's outputs do not depend on how
-  // many streams share the launch.  Their final states stay with the VALU launch below (tiles = 0).
-  auto al16 = [](const void* p, int64_t stride) { return p != nullptr && ((uintptr_t)p % 16) == 0 && stride % 4 == 0; };
-  auto mmable = [&](const StageJob& j, int key) {
-    return j.kind == JK_FIR && j.D == 1 && j.T == key && (j.pre == PRE_NONE || j.pre == PRE_SQUARE) &&
-           al16(j.x, j.x_stride) && (al16(j.y, j.y_stride) || (j.y == nullptr && j.y8 != nullptr)) &&
-           j.n >= (int64_t)MM_MIN_WIN * MM_WT &&
-           j.n % 4 == 0 && j.n < (int64_t)1 << 28;      // (buffer ranges: 32-bit byte offsets)
-  };
-  for (StageJob& j : jobs) j.mma = 0;
-  bool fe_done = fe == nullptr || !fe->on;
-  // the decimate-by-5 LPFs: stage C's stereo mixer + LPF + combiner, stage A's mono LPF
-  // (rx_decmm_kernel; zf and the FE state ride on the launch)
+// Rows the matrix-core kernels take: at least MM_MIN_WIN windows per stream (spans; per-block calls
+// keep the VALU tiles' finer grain), whole 16-B chunks, and 32-bit byte offsets in the buffer ranges
+bool mm_span_ok(int64_t n) { return n >= (int64_t)MM_MIN_WIN * MM_WT && n % 4 == 0 && n < (int64_t)1 << 28; }
+bool al16(const void* p, int64_t stride) { return p != nullptr && ((uintptr_t)p % 16) == 0 && stride % 4 == 0; }
+// A job rx_mma_kernel runs: a D = 1 filter of 101 / 151 taps on 16-B aligned rows -- decided per job
+// from its length alone, so a stream's outputs do not depend on how many streams share the launch.
+// Only such a job may store sign codes (y8) or go without its f32 rows (the receiver asks here too).
+bool mmable(const StageJob& j) {
+  return j.kind == JK_FIR && j.D == 1 && (j.T == 101 || j.T == 151) && (j.pre == PRE_NONE || j.pre == PRE_SQUARE) &&
+         al16(j.x, j.x_stride) && (al16(j.y, j.y_stride) || (j.y == nullptr && j.y8 != nullptr)) && mm_span_ok(j.n);
+}
+
+// The FE state rides on a stage's first launch (fe: still to go, null once aboard)
+void board_fe(StageJobs& Q, const FeState*& fe) {
+  if (fe != nullptr) Q.fe = *fe;
+  fe = nullptr;
+}
+
+// The decimate-by-5 LPFs on the matrix cores: stage C's stereo mixer + LPF + combiner, stage A's
+// mono LPF (rx_decmm_kernel; zf and the FE state ride on the launch)
+hipError_t launch_decmm(std::vector<StageJob>& jobs, int S, hipStream_t st, const FeState*& fe) {
   for (StageJob& j : jobs) {
     const bool mix = j.pre == PRE_NCO && !j.nco_sin && j.mono != nullptr && j.left != nullptr && j.right != nullptr &&
                      j.nco.theta != nullptr && al16(j.mono, j.y_stride) && al16(j.left, j.y_stride) &&
                      al16(j.right, j.y_stride);
     const bool mono = j.pre == PRE_NONE && j.mono == nullptr;
     if (!(j.kind == JK_FIR && j.D == SM_D && j.T == 151 && (mix || mono) && al16(j.y, j.y_stride) &&
-          j.x != nullptr && j.n >= (int64_t)MM_MIN_WIN * MM_WT && j.n < (int64_t)1 << 28 && j.n % 4 == 0))
+          j.x != nullptr && mm_span_ok(j.n)))
       continue;                                      // (n = 0 mod 4: the chunks' edges, mix_load)
     const int64_t wins = (j.n / SM_D + 256) / 256 * S;
     const int wgs = (int)std::min<int64_t>((mix ? sm_wpe<true>() : sm_wpe<false>()) * 256, (wins + 3) / 4);
@@ -1219,10 +1219,7 @@ hipError_t launch_stage(std::vector<StageJob> jobs, int S, hipStream_t st, const
     Q.njobs = 1;
     Q.nstreams = S;
     if (j.zf != nullptr && j.T > 1) Q.zfj[Q.nzf++] = 0;
-    if (!fe_done) {
-      Q.fe = *fe;
-      fe_done = true;
-    }
+    board_fe(Q, fe);
     const unsigned grid = (unsigned)(wgs + Q.nzf * S + (Q.fe.on ? S : 0));
     if (mix && j.nco.th32) hipLaunchKernelGGL((rx_decmm_kernel<true, true>), dim3(grid), dim3(RX_NT), 0, st, Q, wgs);
     else if (mix) hipLaunchKernelGGL(rx_decmm_kernel<true>, dim3(grid), dim3(RX_NT), 0, st, Q, wgs);
@@ -1232,15 +1229,21 @@ hipError_t launch_stage(std::vector<StageJob> jobs, int S, hipStream_t st, const
     j.mma = 1;
     j.zf = nullptr;                                  // (written by that launch)
   }
+  return hipSuccess;
+}
+
+// The D = 1 matrix-core launches (rx_mma_kernel), per tap count
+hipError_t launch_mma(std::vector<StageJob>& jobs, int S, hipStream_t st, const FeState*& fe) {
   for (int key : {151, 101})
     for (int wide : {1, 0}) {                        // groups of 2-3 filters / single filters
       StageJobs Q{};
       Q.nstreams = S;
       std::vector<size_t> members;
+      auto mine = [&](const StageJob& j) { return mmable(j) && j.T == key; };
       for (size_t ji = 0; ji < jobs.size(); ++ji) {
-        if (!mmable(jobs[ji], key) || jobs[ji].mma) continue;
+        if (!mine(jobs[ji]) || jobs[ji].mma) continue;
         int g = 1;                                   // jobs on the same input: one group (<= 3)
-        while (jobs[ji].pre == PRE_NONE && g < 3 && ji + g < jobs.size() && mmable(jobs[ji + g], key) &&
+        while (jobs[ji].pre == PRE_NONE && g < 3 && ji + g < jobs.size() && mine(jobs[ji + g]) &&
                jobs[ji + g].pre == PRE_NONE && jobs[ji + g].x == jobs[ji].x && jobs[ji + g].x_stride == jobs[ji].x_stride &&
                jobs[ji + g].n == jobs[ji].n)
           ++g;
@@ -1277,10 +1280,7 @@ hipError_t launch_stage(std::vector<StageJob> jobs, int S, hipStream_t st, const
         }
       }
       Q.tile_blocks = blocks;
-      if (!fe_done) {                                // the FE state rides on the first launch
-        Q.fe = *fe;
-        fe_done = true;
-      }
+      board_fe(Q, fe);
       const int64_t grid = blocks + (int64_t)Q.nzf * S + (Q.fe.on ? S : 0);
       if (key == 151 && wide) hipLaunchKernelGGL((rx_mma_kernel<151, 3>), dim3((unsigned)grid), dim3(RX_NT), 0, st, Q);
       else if (key == 151) hipLaunchKernelGGL((rx_mma_kernel<151, 1>), dim3((unsigned)grid), dim3(RX_NT), 0, st, Q);
@@ -1293,8 +1293,14 @@ hipError_t launch_stage(std::vector<StageJob> jobs, int S, hipStream_t st, const
         jobs[m].zf = nullptr;                        // (written by that launch)
       }
     }
-  for (const StageJob& j : jobs)                     // sign-code outputs: the matrix-core tiles only
-    if (!j.mma && (j.y8 != nullptr || j.y == nullptr)) return hipErrorInvalidValue;
+  return hipSuccess;
+}
+
+// The VALU launches (rx_stage_kernel), one per tap-count class: the tiles of the jobs the matrix
+// cores did not take, and every final state still to write
+hipError_t launch_valu(const std::vector<StageJob>& jobs, int S, hipStream_t st, const FeState*& fe) {
+  auto cls = [](const StageJob& j) { return (j.kind == JK_FIR && (j.T == 101 || j.T == 151)) ? j.T : 0; };
+  auto outputs = [](const StageJob& j) { return ((j.kind == JK_RESAMPLE ? j.n * j.U : j.n) + j.D - 1) / j.D; };
   for (int key : {151, 101, 0}) {
     StageJobs P{};
     P.nstreams = S;
@@ -1304,10 +1310,7 @@ hipError_t launch_stage(std::vector<StageJob> jobs, int S, hipStream_t st, const
     // in 1 024-output tiles (4 per lane): latency-bound launches get 4x the waves
     int64_t big = 0;
     for (const StageJob& j : jobs)
-      if (cls(j) == key && !j.mma) {
-        const int64_t nout = j.kind == JK_RESAMPLE ? (j.n * j.U + j.D - 1) / j.D : (j.n + j.D - 1) / j.D;
-        big += (nout + 1023) / 1024 * S;
-      }
+      if (cls(j) == key && !j.mma) big += (outputs(j) + 1023) / 1024 * S;
     const bool small = key > 0 && big < 10 * 256;
     // symmetric 151-tap D = 1 jobs on one input, consecutive in the list: folded together (fold_tile)
     auto foldable = [&](const StageJob& a) {
@@ -1319,7 +1322,7 @@ hipError_t launch_stage(std::vector<StageJob> jobs, int S, hipStream_t st, const
       if (cls(j0) != key) continue;
       if (P.njobs == RX_MAXJ) return hipErrorInvalidValue;
       StageJob j = j0;
-      const int64_t nout = j.kind == JK_RESAMPLE ? (j.n * j.U + j.D - 1) / j.D : (j.n + j.D - 1) / j.D;
+      const int64_t nout = outputs(j);
       j.small = (small && j.kind == JK_FIR && j.D == 1) ? 1 : 0;
       j.fold = 0;
       if (follow == 0 && foldable(j)) {
@@ -1338,20 +1341,15 @@ hipError_t launch_stage(std::vector<StageJob> jobs, int S, hipStream_t st, const
       if (j.zf != nullptr && j.T > 1) P.zfj[P.nzf++] = P.njobs;
       P.j[P.njobs++] = j;
     }
-    if (P.njobs == 0 && (fe_done || key != 0)) continue;
-    if (!fe_done) {                       // the FE state rides on the first launch
-      P.fe = *fe;
-      fe_done = true;
-    }
+    if (P.njobs == 0 && (fe == nullptr || key != 0)) continue;
+    board_fe(P, fe);
     P.tile_blocks = blocks;
     const int64_t grid = blocks + (int64_t)P.nzf * S + (P.fe.on ? S : 0);
     if (grid <= 0) continue;
     if (grid > 0x7fffffff) return hipErrorInvalidValue;
-    bool nco = false;
-    for (int i = 0; i < P.njobs; ++i) nco = nco || P.j[i].pre == PRE_NCO;
+    bool nco = false, fold = false;
+    for (int i = 0; i < P.njobs; ++i) nco = nco || P.j[i].pre == PRE_NCO, fold = fold || P.j[i].fold > 1;
     if (nco && key == 0) return hipErrorInvalidValue;     // (the receiver never asks: stage_nco_ok)
-    bool fold = false;
-    for (int i = 0; i < P.njobs; ++i) fold = fold || P.j[i].fold > 1;
     if (fold && (nco || key != 151)) return hipErrorInvalidValue;
     if (fold) hipLaunchKernelGGL((rx_stage_kernel<151, false, true>), dim3((unsigned)grid), dim3(RX_NT), 0, st, P);
     else if (key == 151 && nco) hipLaunchKernelGGL((rx_stage_kernel<151, true>), dim3((unsigned)grid), dim3(RX_NT), 0, st, P);
@@ -1363,6 +1361,18 @@ hipError_t launch_stage(std::vector<StageJob> jobs, int S, hipStream_t st, const
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+// Launch the jobs of one stage: the matrix cores' first, their jobs' final states with them.
+hipError_t launch_stage(std::vector<StageJob> jobs, int S, hipStream_t st, const FeState* fe = nullptr) {
+  for (StageJob& j : jobs) j.mma = 0;
+  if (fe != nullptr && !fe->on) fe = nullptr;
+  hipError_t e = launch_decmm(jobs, S, st, fe);
+  if (e == hipSuccess) e = launch_mma(jobs, S, st, fe);
+  if (e != hipSuccess) return e;
+  for (const StageJob& j : jobs)                     // sign-code outputs: the matrix-core tiles only
+    if (!j.mma && (j.y8 != nullptr || j.y == nullptr)) return hipErrorInvalidValue;
+  return launch_valu(jobs, S, st, fe);
 }
 
 // ---- RDS: I/Q mixers + 3 kHz LPF + x19 zero-stuff + anti-image LPF + [::80] x19 as ONE
@@ -1849,6 +1859,18 @@ enum Zs {
 
 int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
+// What a receiver's blocks decide from its configuration alone (fixed once rx_finalize has run;
+// the PLL loops' constants are not: sdr_rx_set_pll stays legal, so their tables are per call)
+struct RxPlan {
+  bool au, stx, rd;          // the flags: any audio, stereo, RDS
+  bool span;                 // mm_span_ok(M): the rows are long enough for the matrix-core kernels
+  bool codes;                // spans: the PLLs read sign codes that the pilot BPF's and the RDS x^2 + BPF's tiles store
+  bool cres;                 // the RDS LPF + resampler as the composite filter
+  bool tiles_ok;             // the stereo mixer's tiles can form the NCO from the phase rows (PRE_NCO)
+  bool lng; int64_t pb; int nb;   // M is a long PLL call, of nb pseudo-blocks of pb samples
+  bool th32[2];              // per loop: its phase rows in the compact form
+};
+
 }  // namespace
 
 struct sdr_rx {
@@ -1860,6 +1882,7 @@ struct sdr_rx {
   std::vector<double> taps[SDR_RX_NFILTERS];
   PllCfg pll[2] = {};
   bool ready = false;
+  RxPlan plan = {};
   int64_t M = 0, A = 0, R = 0;
   float* out[SDR_RX_NOUTPUTS] = {};    // the rows of the latest block (one of outs[])
   float* outs[3][SDR_RX_NOUTPUTS] = {}; // row sets: nq when pipelined, else one
@@ -1981,6 +2004,30 @@ bool filter_used(const sdr_rx* r, int f) {
 const char* kFilterName[SDR_RX_NFILTERS] = {"rf", "audio", "pilot", "stereo_bpf", "stereo_lpf",
                                             "rds_extract", "rds_square", "rds_lpf", "rds_anti", "rds_rrc"};
 
+RxPlan rx_plan(const sdr_rx* r) {
+  RxPlan p{};
+  p.au = r->flags & (SDR_RX_AUDIO | SDR_RX_STEREO);
+  p.stx = r->flags & SDR_RX_STEREO;
+  p.rd = r->flags & SDR_RX_RDS;
+  p.span = mm_span_ok(r->M);
+  // would launch_stage run filter f of output row `in` on the matrix cores, storing sign codes only?
+  auto mm = [&](int f, int in, int pre) {            // (every row set is aligned alike)
+    StageJob j{};
+    j.kind = JK_FIR; j.D = 1; j.T = (int)r->taps[f].size(); j.pre = pre; j.n = r->M;
+    j.x = r->outs[0][in]; j.x_stride = r->out_stride[in]; j.y8 = r->pcode;
+    return mmable(j);
+  };
+  p.codes = (p.stx || p.rd) && r->pcode != nullptr && (!p.stx || mm(SDR_RX_F_PILOT, SDR_RX_O_DEMOD, PRE_NONE)) &&
+            (!p.rd || mm(SDR_RX_F_RDS_SQUARE, SDR_RX_O_RDS_EXTRACT, PRE_SQUARE));
+  p.cres = p.rd && r->ctaps != nullptr;
+  const int tsl = p.stx ? (int)r->taps[SDR_RX_F_STEREO_LPF].size() : 151;
+  p.tiles_ok = (tsl == 101 || tsl == 151) && (r->audio_decim == 1 || r->audio_decim == 5);
+  p.lng = sdr_pll_long_geom(r->M, &p.pb, &p.nb);
+  p.th32[0] = p.lng && p.pb % TH32_LINE == 0 && p.stx;
+  p.th32[1] = p.lng && p.pb % TH32_LINE == 0 && p.rd;
+  return p;
+}
+
 // Allocate and zero everything once the configuration is known (first block).
 int rx_finalize(sdr_rx* r) {
   for (int f = 0; f < SDR_RX_NFILTERS; ++f)
@@ -2070,6 +2117,7 @@ int rx_finalize(sdr_rx* r) {
     for (int q = 0; q < nsets; ++q) r->pcms[q] = reinterpret_cast<int16_t*>(static_cast<char*>(r->de_mem) + sb + q * pb);
     r->pcm = r->pcms[0];
   }
+  r->plan = rx_plan(r);
   r->ready = true;
   return sdr_rx_reset(r);
 }
@@ -2229,340 +2277,361 @@ int sdr_rx_set_pipeline(sdr_rx* r, int on) {
   return SDR_OK;
 }
 
-int sdr_rx_process_dev(sdr_rx* r, const void* iq, int64_t iq_stride) {
-  if (r == nullptr) return fail(SDR_EINVAL, "sdr_rx is NULL");
-  if (iq == nullptr) return fail(SDR_EINVAL, "sdr_rx_process_dev: iq is NULL");
-  if (r->S > 1 && iq_stride < r->B) return fail(SDR_EINVAL, "sdr_rx_process_dev: iq_stride %lld < block", (long long)iq_stride);
-  if (!r->ready) TRY(rx_finalize(r));
-  sdr_ctx* c = r->c;
-  TRY(set_dev(c));
-  hipStream_t st = c->stream;             // the back half (everything when not pipelined)
+namespace {
+
+// One sdr_rx_process_dev call: the row set and state banks it works on, its streams, the tap sets
+// and what it materialises beyond the plan (sdr_rx_set_keep / the outputs a submit asks for)
+struct RxBlock {
+  sdr_rx* r;
+  int q;                                // row set
+  float** o;                            // its rows
+  double *zi, *zf;                      // lfilter states in / out (the banks swap every block)
+  hipStream_t st, fs;                   // back half (everything when not pipelined), front half
+  const TapSet* ts[SDR_RX_NFILTERS];    // device taps (cached per context; the pointers stay valid for this call)
+  int64_t ms;                           // row stride at the demod rate
+  // Beyond the chain: the NCO rows, and the RDS LPF rows.  Without them the stage-C mixers
+  // form the NCO from the PLL phase rows where they stage their inputs (PRE_NCO, sdr_nco.h) and
+  // the RDS LPF + resampler is the composite filter (rx_cres_kernel), which runs either way.
+  bool nco_rows, lpf_rows;
+  bool de_mono;                         // the de-emphasised mono row of a stereo receiver
+  int8_t* c8;                           // plan.codes: the PLLs' sign-code rows, [PLL k][stream], pcs bytes apart
+  PllJobs P;
+  NcoSrc nsrc[2];                       // per PLL (0 stereo, 1 RDS): where stage C takes its NCO from
+};
+
+bool kept(const sdr_rx* r, int o) { return (r->keep_now >> o) & 1ull; }
+hipError_t mark(const sdr_rx* r, int k, hipStream_t s) { return r->timing ? hipEventRecord(r->ev[k], s) : hipSuccess; }
+const double* zin(const RxBlock& b, int z) { return b.zi + b.r->zoff[z]; }
+double* zout(const RxBlock& b, int z) { return b.zf + b.r->zoff[z]; }
+// block k-nq, the last on this row set, may still run (not when the host has waited for it: submissions)
+bool set_busy(const sdr_rx* r) { return r->blocks >= r->nq && r->blocks - r->nq > r->host_done; }
+
+// What the block leaves in its rows: the configuration's outputs except the intermediates it skipped
+void rx_made(const RxBlock& b) {
+  sdr_rx* r = b.r;
+  for (int o = 0; o < SDR_RX_NOUTPUTS; ++o) {
+    const bool nco_o = o == SDR_RX_O_STEREO_NCO || o == SDR_RX_O_RDS_NCO_I || o == SDR_RX_O_RDS_NCO_Q;
+    const bool lpf_o = o == SDR_RX_O_RDS_LPF_I || o == SDR_RX_O_RDS_LPF_Q;
+    const bool pin_o = o == SDR_RX_O_BPF_RECOVERY || o == SDR_RX_O_RDS_PRE_PLL;      // (codes: when kept)
+    r->made[o] = need_out(r, o) && (!nco_o || b.nco_rows) && (!lpf_o || b.lpf_rows) && (!pin_o || !r->plan.codes || kept(r, o)) &&
+                 (o != SDR_RX_O_AUDIO_DE || !r->plan.stx || b.de_mono);
+  }
+}
+
+// Filter f (state slot z) from the first n samples of output row xo into output row yo (and its
+// host mirror); co: a PRE_MIX second operand's row
+StageJob fir(const RxBlock& b, int f, int z, int xo, int64_t n, int yo, int D, int pre = PRE_NONE, int co = -1) {
+  const sdr_rx* r = b.r;
+  StageJob j{};
+  j.x = b.o[xo]; j.x_stride = r->out_stride[xo]; j.n = n; j.c = co < 0 ? nullptr : b.o[co];
+  j.taps = b.ts[f]->dev_f32; j.rtaps = b.ts[f]->dev_rev; j.taps64 = b.ts[f]->dev_f64;
+  j.zi = zin(b, z); j.zf = zout(b, z); j.zi_stride = r->zlen[z];
+  j.y = b.o[yo]; j.y_stride = r->out_stride[yo]; j.yh = r->mirror[yo]; j.yh_stride = r->out_n[yo];
+  j.gain = 2.0f;                      // the reference's mixer gain (fmMonoBlock.py:156, fmRDSblock.py:173)
+  j.pre = pre; j.D = D; j.U = 1; j.kind = JK_FIR; j.T = (int)r->taps[f].size();
+  j.sym = b.ts[f]->sym;               // fold_tile may take it
+  return j;
+}
+
+// Spans (the matrix-core rows): the PLLs take their inputs as sign codes (sdr_nco.h pll_code,
+// r06) -- all the recurrence reads of them -- stored by the pilot BPF's and the RDS x^2 + BPF's
+// tiles beside (or, when those rows are not kept, instead of) their f32 rows
+StageJob coded(const RxBlock& b, StageJob j, int k, int o) {
+  if (b.r->plan.codes) {
+    j.y8 = b.c8 + (int64_t)k * b.r->S * b.r->pcs;
+    j.y8_stride = b.r->pcs;
+    if (!kept(b.r, o)) j.y = nullptr;
+  }
+  return j;
+}
+
+// Front half: FE, stage A, stage B.
+int rx_front(RxBlock& b, const void* iq, int64_t xs, bool fast) {
+  sdr_rx* r = b.r;
+  const RxPlan& pl = r->plan;
   const int S = r->S;
-  const int64_t M = r->M;
-  double* zi = r->bank[r->parity];
-  double* zf = r->bank[r->parity ^ 1];
-  const int q = r->pipe ? (int)(r->blocks % r->nq) : 0;
+  const int64_t M = r->M, ms = b.ms;
+  hipStream_t fs = b.fs;
+  if (r->pipe) {
+    // states of block k-1 (r04b: not when its front half ran on this same stream, in order)
+    if (r->blocks >= 1 && r->last_fs != fs) HIP_TRY(hipStreamWaitEvent(fs, r->ev_front[(b.q + r->nq - 1) % r->nq], 0));
+    r->last_fs = fs;
+    if (set_busy(r)) HIP_TRY(hipStreamWaitEvent(fs, r->ev_back[b.q], 0));
+  }
+  HIP_TRY(mark(r, 0, fs));
   // FE: RF FIR + decimate + demod (fe.hip).  The tiled kernels take the reference's RF
   // configurations; their carried state (I/Q zf, demod phase) is finished by workgroups of
   // the stage-A launch.  Other configurations run sdr_rf_frontend_dev's generic path (on the
   // context stream, so a pipelined receiver's front half runs there for such blocks).
+  const TapSet* rf = b.ts[SDR_RX_F_RF];
   const int Trf = (int)r->taps[SDR_RX_F_RF].size();
-  const int64_t xs = S > 1 ? iq_stride : r->B;
-  const int G = r->u8 ? 8 : 2;
-  const bool fast = (Trf == 101 || Trf == 151) && r->rf_decim == 10 && (S <= 1 || r->u8 || xs % G == 0) &&
-                    ((uintptr_t)iq % (r->u8 ? 4 : 16)) == 0;
-  hipStream_t fs = (r->pipe && fast) ? r->front : st;
-  if (r->pipe) {
-    // states of block k-1 (r04b: not when its front half ran on this same stream, in order)
-    if (r->blocks >= 1 && r->last_fs != fs) HIP_TRY(hipStreamWaitEvent(fs, r->ev_front[(q + r->nq - 1) % r->nq], 0));
-    r->last_fs = fs;
-    // set q read by k-nq (not when the host has already waited for that block: submissions)
-    if (r->blocks >= r->nq && r->blocks - r->nq > r->host_done) HIP_TRY(hipStreamWaitEvent(fs, r->ev_back[q], 0));
-  }
-  auto mark = [&](int k, hipStream_t s) { return r->timing ? hipEventRecord(r->ev[k], s) : hipSuccess; };
-  HIP_TRY(mark(0, fs));
-  auto zin = [&](int z) { return zi + r->zoff[z]; };
-  auto out_of = [&](const float* y) {
-    for (int o = 0; o < SDR_RX_NOUTPUTS; ++o)
-      if (r->outs[q][o] == y && need_out(r, o)) return o;
-    return -1;
-  };
-  auto mirror_of = [&](const float* y) { const int o = out_of(y); return o < 0 ? nullptr : r->mirror[o]; };
-  auto host_n = [&](const float* y) { const int o = out_of(y); return o < 0 ? (int64_t)0 : r->out_n[o]; };
-  auto zout = [&](int z) { return zf + r->zoff[z]; };
-  // device taps (cached per context; the pointers stay valid for this call)
-  const TapSet* ts[SDR_RX_NFILTERS] = {};
-  for (int f = 0; f < SDR_RX_NFILTERS; ++f)
-    if (filter_used(r, f)) TRY(get_taps(c, r->taps[f].data(), (int)r->taps[f].size(), &ts[f]));
-  float** o = r->outs[q];
-  const int64_t ms = r->out_stride[SDR_RX_O_DEMOD];
   FeState fst{};
   if (fast) {
+    const int G = r->u8 ? 8 : 2;
     const int64_t fstride = S > 1 ? xs : ceil_div(r->B, G) * G;
-    FeLaunch a{iq, r->B, fstride, 0, S, ts[SDR_RX_F_RF]->dev_f32, &ts[SDR_RX_F_RF]->h, Trf, r->rf_decim, r->u8,
-               zin(Z_FE_I), zin(Z_FE_Q), r->zlen[Z_FE_I], r->phase, o[SDR_RX_O_DEMOD], ms, nullptr, nullptr,
-               r->last_phi, r->wraps, ts[SDR_RX_F_RF]->dev_afr};
+    FeLaunch a{iq, r->B, fstride, 0, S, rf->dev_f32, &rf->h, Trf, r->rf_decim, r->u8,
+               zin(b, Z_FE_I), zin(b, Z_FE_Q), r->zlen[Z_FE_I], r->phase, b.o[SDR_RX_O_DEMOD], ms, nullptr, nullptr,
+               r->last_phi, r->wraps, rf->dev_afr};
     HIP_TRY(sdr_launch_fe(a, fs));
-    fst = FeState{iq, r->B, xs, ts[SDR_RX_F_RF]->dev_f64, zin(Z_FE_I), zin(Z_FE_Q), zout(Z_FE_I), zout(Z_FE_Q),
+    fst = FeState{iq, r->B, xs, rf->dev_f64, zin(b, Z_FE_I), zin(b, Z_FE_Q), zout(b, Z_FE_I), zout(b, Z_FE_Q),
                   r->zlen[Z_FE_I], r->last_phi, r->wraps, r->phase, Trf, r->u8, 1};
   } else {
-    TRY(sdr_rf_frontend_dev(c, iq, r->u8 ? SDR_IQ_U8 : SDR_IQ_F32, r->B, xs, 0, S, r->taps[SDR_RX_F_RF].data(),
-                            Trf, r->rf_decim, zin(Z_FE_I), zin(Z_FE_Q), r->zlen[Z_FE_I], zout(Z_FE_I), zout(Z_FE_Q),
-                            r->phase, o[SDR_RX_O_DEMOD], ms, nullptr, nullptr));
+    TRY(sdr_rf_frontend_dev(r->c, iq, r->u8 ? SDR_IQ_U8 : SDR_IQ_F32, r->B, xs, 0, S, r->taps[SDR_RX_F_RF].data(),
+                            Trf, r->rf_decim, zin(b, Z_FE_I), zin(b, Z_FE_Q), r->zlen[Z_FE_I], zout(b, Z_FE_I),
+                            zout(b, Z_FE_Q), r->phase, b.o[SDR_RX_O_DEMOD], ms, nullptr, nullptr));
   }
-  HIP_TRY(mark(1 + SDR_RX_ST_FE, fs));
-  auto fir = [&](int f, int z, const float* x, int64_t n, int64_t xs, float* y, int64_t ys, int D, int pre = PRE_NONE,
-                 const float* cmix = nullptr) {
-    StageJob j{};
-    j.x = x; j.c = cmix; j.taps = ts[f]->dev_f32; j.rtaps = ts[f]->dev_rev; j.taps64 = ts[f]->dev_f64;
-    j.zi = zin(z); j.zf = zout(z); j.zi_stride = r->zlen[z];
-    j.y = y; j.y_stride = ys; j.n = n; j.x_stride = xs;
-    j.gain = 2.0f;                      // the reference's mixer gain (fmMonoBlock.py:156, fmRDSblock.py:173)
-    j.pre = pre; j.D = D; j.U = 1; j.kind = JK_FIR; j.T = (int)r->taps[f].size();
-    j.sym = 1;                          // linear phase (f32 taps mirror-equal): fold_tile may take it
-    for (int k = 0; k < j.T / 2 && j.T <= SDR_MAX_TAPS; ++k)
-      if (ts[f]->h.h[k] != ts[f]->h.h[j.T - 1 - k]) j.sym = 0;
-    j.yh = mirror_of(y);
-    j.yh_stride = host_n(y);
-    return j;
-  };
-  const bool au = r->flags & (SDR_RX_AUDIO | SDR_RX_STEREO), stx = r->flags & SDR_RX_STEREO,
-             rd = r->flags & SDR_RX_RDS;
-  const int64_t as = au ? r->out_stride[SDR_RX_O_AUDIO] : 0;
-  // What this block materialises beyond what the chain needs (sdr_rx_set_keep / the outputs a
-  // submit asks for)
-  auto kept = [&](int o) { return (r->keep_now >> o) & 1ull; };
-  // Spans (the matrix-core rows): the PLLs take their inputs as sign codes (sdr_nco.h pll_code,
-  // r06) -- all the recurrence reads of them -- stored by the pilot BPF's and the RDS x^2 + BPF's
-  // tiles beside (or, when those rows are not kept, instead of) their f32 rows
-  auto mm_taps = [&](int f) { const size_t t = r->taps[f].size(); return t == 101 || t == 151; };
-  const bool codes = (stx || rd) && r->pcode != nullptr && M >= (int64_t)MM_MIN_WIN * MM_WT && M % 4 == 0 &&
-                     M < ((int64_t)1 << 28) && (!stx || mm_taps(SDR_RX_F_PILOT)) && (!rd || mm_taps(SDR_RX_F_RDS_SQUARE));
-  int8_t* c8 = codes ? r->pcode + (int64_t)q * 2 * S * r->pcs : nullptr;   // [PLL k][stream] rows, pcs bytes apart
-  auto coded = [&](StageJob j, int k, int o) {
-    if (codes) {
-      j.y8 = c8 + (int64_t)k * S * r->pcs;
-      j.y8_stride = r->pcs;
-      if (!kept(o)) j.y = nullptr;
-    }
-    return j;
-  };
+  HIP_TRY(mark(r, 1 + SDR_RX_ST_FE, fs));
   // stage A: every filter of the demodulated signal (model/fmMonoBlock.py:101-105, :117,
   // :151; model/fmRDSblock.py:156)
   std::vector<StageJob> A;
-  if (au) A.push_back(fir(SDR_RX_F_AUDIO, Z_AUDIO, o[SDR_RX_O_DEMOD], M, ms, o[SDR_RX_O_AUDIO], as, r->audio_decim));
-  if (stx) {
-    A.push_back(coded(fir(SDR_RX_F_PILOT, Z_PILOT, o[SDR_RX_O_DEMOD], M, ms, o[SDR_RX_O_BPF_RECOVERY], ms, 1), 0,
-                      SDR_RX_O_BPF_RECOVERY));
-    A.push_back(fir(SDR_RX_F_STEREO_BPF, Z_BAND, o[SDR_RX_O_DEMOD], M, ms, o[SDR_RX_O_BPF_EXTRACTION], ms, 1));
+  if (pl.au) A.push_back(fir(b, SDR_RX_F_AUDIO, Z_AUDIO, SDR_RX_O_DEMOD, M, SDR_RX_O_AUDIO, r->audio_decim));
+  if (pl.stx) {
+    A.push_back(coded(b, fir(b, SDR_RX_F_PILOT, Z_PILOT, SDR_RX_O_DEMOD, M, SDR_RX_O_BPF_RECOVERY, 1), 0, SDR_RX_O_BPF_RECOVERY));
+    A.push_back(fir(b, SDR_RX_F_STEREO_BPF, Z_BAND, SDR_RX_O_DEMOD, M, SDR_RX_O_BPF_EXTRACTION, 1));
   }
-  if (rd) A.push_back(fir(SDR_RX_F_RDS_EXTRACT, Z_EXTRACT, o[SDR_RX_O_DEMOD], M, ms, o[SDR_RX_O_RDS_EXTRACT], ms, 1));
+  if (pl.rd) A.push_back(fir(b, SDR_RX_F_RDS_EXTRACT, Z_EXTRACT, SDR_RX_O_DEMOD, M, SDR_RX_O_RDS_EXTRACT, 1));
   HIP_TRY(launch_stage(A, S, fs, &fst));
-  HIP_TRY(mark(1 + SDR_RX_ST_A, fs));
+  HIP_TRY(mark(r, 1 + SDR_RX_ST_A, fs));
   // stage B: RDS squaring non-linearity + BPF (model/fmRDSblock.py:161-164)
-  if (rd) HIP_TRY(launch_stage({coded(fir(SDR_RX_F_RDS_SQUARE, Z_SQUARE, o[SDR_RX_O_RDS_EXTRACT], M, ms,
-                                          o[SDR_RX_O_RDS_PRE_PLL], ms, 1, PRE_SQUARE), 1, SDR_RX_O_RDS_PRE_PLL)}, S, fs));
-  HIP_TRY(mark(1 + SDR_RX_ST_B, fs));
-  // PLLs (model/fmMonoBlock.py:119, model/fmRDSblock.py:167): one lane per recurrence.
-  // Pipelined, the three launches go to three streams: the per-sample constants with the
-  // front half (trigOffset = M x blocks since reset, known here), the recurrence alone on
-  // its own stream -- block k's starts as soon as block k-1's is done, beside block k-1's
-  // NCO and stages C-E and block k+1's front half -- and the NCO with the back half.  Phase
-  // and constant rows alternate with the row set; set q is free once block k-2's back half
-  // (which waited for its recurrence) is done.
-  const bool plls = stx || rd;
-  // Beyond the chain: the NCO rows, and the RDS LPF rows.  Without them the stage-C mixers
-  // form the NCO from the PLL phase rows where they stage their inputs (PRE_NCO, sdr_nco.h) and
-  // the RDS LPF + resampler is the composite filter (rx_cres_kernel), which runs either way.
-  const bool cres = rd && r->ctaps != nullptr;
-  const int tsl = stx ? (int)r->taps[SDR_RX_F_STEREO_LPF].size() : 151;
-  const bool tiles_ok = (tsl == 101 || tsl == 151) && (r->audio_decim == 1 || r->audio_decim == 5);   // PRE_NCO tiles
-  const bool nco_rows = (stx && kept(SDR_RX_O_STEREO_NCO)) || (rd && (kept(SDR_RX_O_RDS_NCO_I) || kept(SDR_RX_O_RDS_NCO_Q))) ||
-                        M < 2 || (rd && !cres) || !tiles_ok;
-  const bool lpf_rows = rd && (!cres || kept(SDR_RX_O_RDS_LPF_I) || kept(SDR_RX_O_RDS_LPF_Q));
-  // The recurrences get a stream of their own (block k's beside block k-1's NCO and stages
-  // C-E) whenever the receiver is pipelined.  Round 4 kept a few per-block recurrences (c4:
-  // one, ~26 us) on the back stream, where each cross-stream hop then cost more than the
-  // overlap returned (c4 790-840 -> 950 MS/s); with two blocks in flight and the trimmed
-  // event calls (r04b) the hop pays: c4 1 022 -> 1 090 MS/s (medians of 8 interleaved runs,
-  // profiles/r04/iter/r04b/pllstream/).
-  const bool mid = r->pipe;
-  hipStream_t ps = mid ? r->mid : st;
-  PllJobs P{};
-  NcoSrc nsrc[2] = {};                 // per PLL (0 stereo, 1 RDS): where stage C takes its NCO from
+  if (pl.rd) HIP_TRY(launch_stage({coded(b, fir(b, SDR_RX_F_RDS_SQUARE, Z_SQUARE, SDR_RX_O_RDS_EXTRACT, M, SDR_RX_O_RDS_PRE_PLL,
+                                                 1, PRE_SQUARE), 1, SDR_RX_O_RDS_PRE_PLL)}, S, fs));
+  HIP_TRY(mark(r, 1 + SDR_RX_ST_B, fs));
+  return SDR_OK;
+}
+
+// Loop k's job (b.P) and where stage C takes its NCO from (b.nsrc[k]).  The tables follow the
+// loop's current configuration (sdr_rx_set_pll is legal between blocks).
+int rx_pll_job(RxBlock& b, int k, int in, int nco_i, int nco_q) {
+  sdr_rx* r = b.r;
+  const RxPlan& pl = r->plan;
+  const int S = r->S;
+  const int64_t M = r->M, ms = b.ms;
+  PllJobs& P = b.P;
+  float *ni = b.o[nco_i], *nq = nco_q < 0 ? nullptr : b.o[nco_q];
+  double* thk = r->theta + ((int64_t)b.q * 2 + k) * S * r->ths;
+  double* pck = r->pllc + ((int64_t)b.q * 2 + k) * S * r->cst;
+  const double* resp = nullptr;
+  const double* qtab = nullptr;
+  TRY(get_resp(r->c, r->pll[k], M, &resp));
+  TRY(get_qtab(r->c, r->pll[k], &qtab));
+  const int jq = P.njobs;
+  P.j[P.njobs++] = PllJob{b.o[in], ms, r->pll_state[k], thk, r->ths, ni, nq, ms, r->pll[k], pck, r->cst,
+                          (double)M * (double)r->blocks, 1, resp, qtab};
+  if (pl.codes) {
+    P.j[jq].in8 = b.c8 + (int64_t)k * S * r->pcs;
+    P.j[jq].in8_stride = r->pcs;
+  }
+  NcoSrc& N = b.nsrc[k];
+  N.theta = M >= 2 ? thk : nullptr;   // (M < 2: the sequential kernels' Q-form rows; mix from the NCO rows)
+  // compact phase rows (sdr_nco.h, r06): half the bytes of the solve's stores and of the mixers'
+  // loads.  Every reader decodes them, so the form depends on the geometry alone, not on a block's keep
+  if (pl.th32[k]) P.j[jq].th32 = N.th32 = 1;
+  N.th_stride = r->ths; N.n = M;
+  N.nco_i = ni; N.nco_q = nq; N.out_stride = ms;
+  N.w = 2.0 * M_PI * (r->pll[k].freq / r->pll[k].fs); N.scale = r->pll[k].scale; N.adj = r->pll[k].adj;
+  if (pl.lng) {                                            // the records follow (stx + rd) x S headers
+    N.blk = long_blk0(P.work, (int)pl.stx + (int)pl.rd, S, pl.nb, jq * S);
+    N.blk_stride = N.nb = pl.nb; N.pb = pl.pb;
+    N.resp = resp; N.resp32 = resp32_of(resp, pl.pb);
+  }
+  return SDR_OK;
+}
+
+// PLLs (model/fmMonoBlock.py:119, model/fmRDSblock.py:167): one lane per recurrence.
+// Pipelined, the three launches go to three streams: the per-sample constants with the
+// front half (trigOffset = M x blocks since reset, known here), the recurrence alone on
+// its own stream -- block k's starts as soon as block k-1's is done, beside block k-1's
+// NCO and stages C-E and block k+1's front half -- and the NCO with the back half.  Phase
+// and constant rows alternate with the row set; set q is free once block k-2's back half
+// (which waited for its recurrence) is done.
+int rx_pll(RxBlock& b) {
+  sdr_rx* r = b.r;
+  const RxPlan& pl = r->plan;
+  const int q = b.q;
+  PllJobs& P = b.P;
+  const bool plls = pl.stx || pl.rd;
+  hipStream_t ps = r->pipe ? r->mid : b.st;          // the recurrences' own stream when pipelined
   if (plls) {
-    P.nstreams = S;
-    P.n = M;
-    P.stats = c->pll_stats;
-    P.nco_rows = nco_rows ? 1 : 0;
+    P.nstreams = r->S;
+    P.n = r->M;
+    P.stats = r->c->pll_stats;
+    P.nco_rows = b.nco_rows ? 1 : 0;
     P.work = r->pllw_bytes ? r->pllw + (int64_t)q * r->pllw_bytes : nullptr;
-    double* th = r->theta + (int64_t)q * 2 * S * r->ths;
-    double* pc = r->pllc + (int64_t)q * 2 * S * r->cst;
-    const double off = (double)M * (double)r->blocks;
-    int64_t pb = 0;
-    int nb = 0;
-    const bool lng = sdr_pll_long_geom(M, &pb, &nb);
-    // the loops' phase rows in the compact form (sdr_nco.h, r06): half the bytes of the solve's
-    // stores and of the mixers' loads.  Every reader decodes them -- the matrix-core mixers
-    // (TH32 forms), the VALU tiles and final states (nco_f32x4, nco_at), the NCO kernel -- so
-    // the form depends only on the call's geometry (pseudo-blocks on a line), never on what a
-    // block keeps
-#ifdef SDR_NO_TH32   // diagnostic builds only (tools/build_dbg.sh): the full rows, for an A/B of the outputs
-    const bool th32 = false, th32r = false;
-#else
-    const bool th32 = lng && pb % TH32_LINE == 0 && stx, th32r = lng && pb % TH32_LINE == 0 && rd;
-#endif
-    auto add = [&](int k, const float* in, double* thk, float* ni, float* nq, double* pck) -> int {
-      const double* resp = nullptr;
-      TRY(get_resp(c, r->pll[k], M, &resp));
-      const int jq = P.njobs;
-      P.j[P.njobs++] = PllJob{in, ms, r->pll_state[k], thk, r->ths, ni, nq, ms, r->pll[k], pck, r->cst, off, 1, resp};
-      if (codes) {
-        P.j[jq].in8 = c8 + (int64_t)k * S * r->pcs;
-        P.j[jq].in8_stride = r->pcs;
-      }
-      NcoSrc& N = nsrc[k];
-      N.theta = M >= 2 ? thk : nullptr;   // (M < 2: the sequential kernels' Q-form rows; mix from the NCO rows)
-      if ((k == 0 && th32) || (k == 1 && th32r)) P.j[jq].th32 = N.th32 = 1;
-      N.th_stride = r->ths;
-      N.nco_i = ni;
-      N.nco_q = nq;
-      N.out_stride = ms;
-      N.w = 2.0 * M_PI * (r->pll[k].freq / r->pll[k].fs);
-      N.scale = r->pll[k].scale;
-      N.adj = r->pll[k].adj;
-      N.n = M;
-      if (lng) {
-        N.blk = long_blk0(P.work, 0, S, nb, jq * S);        // njobs fixed up below
-        N.blk_stride = nb;
-        N.nb = nb;
-        N.pb = pb;
-        N.resp = resp;
-        N.resp32 = resp32_of(resp, pb);
-      }
-      return SDR_OK;
-    };
-    if (stx) TRY(add(0, o[SDR_RX_O_BPF_RECOVERY], th, o[SDR_RX_O_STEREO_NCO], nullptr, pc));
-    if (rd) TRY(add(1, o[SDR_RX_O_RDS_PRE_PLL], th + (int64_t)S * r->ths, o[SDR_RX_O_RDS_NCO_I], o[SDR_RX_O_RDS_NCO_Q],
-                    pc + (int64_t)S * r->cst));
-    if (lng)                                                // the records follow P.njobs x S headers
-      for (NcoSrc& N : nsrc)
-        if (N.blk) N.blk = reinterpret_cast<const LongBlk*>(reinterpret_cast<const char*>(N.blk) +
-                                                              (int64_t)P.njobs * S * sizeof(LongHdr));
-    HIP_TRY(sdr_launch_pll_prep(P, fs));
+    if (pl.stx) TRY(rx_pll_job(b, 0, SDR_RX_O_BPF_RECOVERY, SDR_RX_O_STEREO_NCO, -1));
+    if (pl.rd) TRY(rx_pll_job(b, 1, SDR_RX_O_RDS_PRE_PLL, SDR_RX_O_RDS_NCO_I, SDR_RX_O_RDS_NCO_Q));
+    HIP_TRY(sdr_launch_pll_prep(P, b.fs));
   }
   if (r->pipe) {
-    HIP_TRY(hipEventRecord(r->ev_front[q], fs));
-    if (plls && mid) {
+    HIP_TRY(hipEventRecord(r->ev_front[q], b.fs));
+    if (plls) {
       HIP_TRY(hipStreamWaitEvent(ps, r->ev_front[q], 0));
-      if (r->blocks >= r->nq && r->blocks - r->nq > r->host_done) HIP_TRY(hipStreamWaitEvent(ps, r->ev_back[q], 0));
+      if (set_busy(r)) HIP_TRY(hipStreamWaitEvent(ps, r->ev_back[q], 0));
     } else {
-      HIP_TRY(hipStreamWaitEvent(st, r->ev_front[q], 0));
+      HIP_TRY(hipStreamWaitEvent(b.st, r->ev_front[q], 0));
     }
   }
   if (plls) HIP_TRY(sdr_launch_pll_loop(P, ps));
-  HIP_TRY(mark(1 + SDR_RX_ST_PLL, ps));
-  if (mid && plls) {
+  HIP_TRY(mark(r, 1 + SDR_RX_ST_PLL, ps));
+  if (r->pipe && plls) {
     HIP_TRY(hipEventRecord(r->ev_mid[q], ps));
-    HIP_TRY(hipStreamWaitEvent(st, r->ev_mid[q], 0));
+    HIP_TRY(hipStreamWaitEvent(b.st, r->ev_mid[q], 0));
   }
-  if (plls) HIP_TRY(sdr_launch_pll_nco(P, st));
+  if (plls) HIP_TRY(sdr_launch_pll_nco(P, b.st));
+  return SDR_OK;
+}
+
+// stage D with the composite filter: the RDS mixers + LPF + x19 / 80 resampler in one kernel, and
+// the LPF's and anti-image filter's final states
+int rx_cres(const RxBlock& b) {
+  const sdr_rx* r = b.r;
+  const int S = r->S;
+  float** o = b.o;
+  CresJob J{};
+  J.x = o[SDR_RX_O_RDS_EXTRACT]; J.n = r->M; J.x_stride = b.ms;
+  J.nco = b.nsrc[1];
+  J.ctaps = r->ctaps; J.h64 = b.ts[SDR_RX_F_RDS_LPF]->dev_f64; J.g64 = b.ts[SDR_RX_F_RDS_ANTI]->dev_f64;
+  J.zi_l[0] = zin(b, Z_RLPF_I); J.zi_l[1] = zin(b, Z_RLPF_Q);
+  J.zi_a[0] = zin(b, Z_ANTI_I); J.zi_a[1] = zin(b, Z_ANTI_Q);
+  J.zf_l[0] = zout(b, Z_RLPF_I); J.zf_l[1] = zout(b, Z_RLPF_Q);
+  J.zf_a[0] = zout(b, Z_ANTI_I); J.zf_a[1] = zout(b, Z_ANTI_Q);
+  J.zs = r->zlen[Z_RLPF_I];
+  J.y[0] = o[SDR_RX_O_RDS_RES_I]; J.y[1] = o[SDR_RX_O_RDS_RES_Q];
+  J.yh[0] = r->mirror[SDR_RX_O_RDS_RES_I]; J.yh[1] = r->mirror[SDR_RX_O_RDS_RES_Q];
+  J.y_stride = r->out_stride[SDR_RX_O_RDS_RES_I]; J.yh_stride = r->out_n[SDR_RX_O_RDS_RES_I];
+  J.R = r->R; J.tiles = (int)ceil_div(r->R, CR_TO); J.nstreams = S;
+  const int64_t grid = (int64_t)J.tiles * S + S;
+  if (grid > 0x7fffffff || r->zlen[Z_ANTI_I] != J.zs) return fail(SDR_EINVAL, "sdr_rx: composite RDS geometry");
+  // spans: the matrix-core form (per job length, as launch_stage decides: a stream's outputs
+  // do not depend on how many streams share the launch)
+  if (r->plan.span && J.nco.theta != nullptr) {
+    const int64_t wins = ceil_div(r->R, CM_WO) * S;
+    const int wgs = (int)std::min<int64_t>(CM_WGS, ceil_div(wins, 4));
+    if (J.nco.th32)
+      hipLaunchKernelGGL(rx_cresmm_kernel<true>, dim3((unsigned)(S + wgs)), dim3(RX_NT), 0, b.st, J, r->ctaps + CR_NTAPS, wgs);
+    else
+      hipLaunchKernelGGL(rx_cresmm_kernel<false>, dim3((unsigned)(S + wgs)), dim3(RX_NT), 0, b.st, J, r->ctaps + CR_NTAPS, wgs);
+  } else {
+    hipLaunchKernelGGL(rx_cres_kernel, dim3((unsigned)grid), dim3(CR_NT), 0, b.st, J);
+  }
+  HIP_TRY(hipGetLastError());
+  return SDR_OK;
+}
+
+// a stage-C mixer: the NCO from loop k's phase rows (PRE_NCO) where the tiles can form it
+StageJob mixer(const RxBlock& b, StageJob j, int k, int sin_) {
+  if (b.nsrc[k].theta != nullptr && (j.T == 101 || j.T == 151) && (j.D == 1 || j.D == 5)) {
+    j.pre = PRE_NCO;
+    j.nco = b.nsrc[k];
+    j.nco_sin = sin_;
+    j.c = nullptr;
+  }
+  return j;
+}
+
+// Back half: stage C, the composite or two-stage D, E, the audio output stage.
+int rx_back(RxBlock& b) {
+  sdr_rx* r = b.r;
+  const RxPlan& pl = r->plan;
+  const int S = r->S;
+  const int64_t M = r->M;
+  float** o = b.o;
+  hipStream_t st = b.st;
   // stage C: the stereo mixer + LPF (its store also forms L and R); the RDS I/Q mixer + LPF
   // rows only when they are kept (or without the composite filter)
-  auto mixer = [&](StageJob j, int k, int sin_) {
-    if (nsrc[k].theta != nullptr && (j.T == 101 || j.T == 151) && (j.D == 1 || j.D == 5)) {
-      j.pre = PRE_NCO;
-      j.nco = nsrc[k];
-      j.nco_sin = sin_;
-      j.c = nullptr;
-    }
-    return j;
-  };
   std::vector<StageJob> C;
-  if (stx) {
-    StageJob j = fir(SDR_RX_F_STEREO_LPF, Z_SLPF, o[SDR_RX_O_BPF_EXTRACTION], M, ms, o[SDR_RX_O_STEREO], as,
-                     r->audio_decim, PRE_MIX, o[SDR_RX_O_STEREO_NCO]);          // fmMonoBlock.py:155-162
+  if (pl.stx) {
+    StageJob j = fir(b, SDR_RX_F_STEREO_LPF, Z_SLPF, SDR_RX_O_BPF_EXTRACTION, M, SDR_RX_O_STEREO, r->audio_decim,
+                     PRE_MIX, SDR_RX_O_STEREO_NCO);                             // fmMonoBlock.py:155-162
     j.mono = o[SDR_RX_O_AUDIO];                                                 // :166-170 (intended)
     j.left = o[SDR_RX_O_LEFT];
     j.right = o[SDR_RX_O_RIGHT];
-    j.lh = r->mirror[SDR_RX_O_LEFT];
-    j.rh = r->mirror[SDR_RX_O_RIGHT];
-    j.yh_stride = r->out_n[SDR_RX_O_STEREO];                                    // == out_n of L and R
-    C.push_back(mixer(j, 0, 0));
+    j.lh = r->mirror[SDR_RX_O_LEFT];                                            // (yh_stride: out_n of stereo,
+    j.rh = r->mirror[SDR_RX_O_RIGHT];                                           //  == out_n of L and R)
+    C.push_back(mixer(b, j, 0, 0));
   }
-  if (lpf_rows) {                                                              // fmRDSblock.py:173-182
+  if (b.lpf_rows) {                                                            // fmRDSblock.py:173-182
     for (int k = 0; k < 2; ++k) {
-      StageJob j = fir(SDR_RX_F_RDS_LPF, k ? Z_RLPF_Q : Z_RLPF_I, o[SDR_RX_O_RDS_EXTRACT], M, ms,
-                       o[k ? SDR_RX_O_RDS_LPF_Q : SDR_RX_O_RDS_LPF_I], ms, 1, PRE_MIX,
-                       o[k ? SDR_RX_O_RDS_NCO_Q : SDR_RX_O_RDS_NCO_I]);
-      if (cres) j.zf = nullptr;                 // the composite kernel writes the LPF's final states
-      C.push_back(mixer(j, 1, k));
+      StageJob j = fir(b, SDR_RX_F_RDS_LPF, k ? Z_RLPF_Q : Z_RLPF_I, SDR_RX_O_RDS_EXTRACT, M,
+                       k ? SDR_RX_O_RDS_LPF_Q : SDR_RX_O_RDS_LPF_I, 1, PRE_MIX, k ? SDR_RX_O_RDS_NCO_Q : SDR_RX_O_RDS_NCO_I);
+      if (pl.cres) j.zf = nullptr;              // the composite kernel writes the LPF's final states
+      C.push_back(mixer(b, j, 1, k));
     }
   }
   HIP_TRY(launch_stage(C, S, st));
-  HIP_TRY(mark(1 + SDR_RX_ST_C, st));
-  if (rd) {
-    const int64_t rs = r->out_stride[SDR_RX_O_RDS_RES_I];
-    if (cres) {
-      // stage D: the RDS mixers + LPF + x19 / 80 resampler as one composite filter, and the
-      // LPF's and anti-image filter's final states
-      CresJob J{};
-      J.x = o[SDR_RX_O_RDS_EXTRACT];
-      J.n = M;
-      J.x_stride = ms;
-      J.nco = nsrc[1];
-      J.ctaps = r->ctaps;
-      J.h64 = ts[SDR_RX_F_RDS_LPF]->dev_f64;
-      J.g64 = ts[SDR_RX_F_RDS_ANTI]->dev_f64;
-      J.zi_l[0] = zin(Z_RLPF_I); J.zi_l[1] = zin(Z_RLPF_Q);
-      J.zi_a[0] = zin(Z_ANTI_I); J.zi_a[1] = zin(Z_ANTI_Q);
-      J.zf_l[0] = zout(Z_RLPF_I); J.zf_l[1] = zout(Z_RLPF_Q);
-      J.zf_a[0] = zout(Z_ANTI_I); J.zf_a[1] = zout(Z_ANTI_Q);
-      J.zs = r->zlen[Z_RLPF_I];
-      J.y[0] = o[SDR_RX_O_RDS_RES_I]; J.y[1] = o[SDR_RX_O_RDS_RES_Q];
-      J.yh[0] = r->mirror[SDR_RX_O_RDS_RES_I]; J.yh[1] = r->mirror[SDR_RX_O_RDS_RES_Q];
-      J.y_stride = rs;
-      J.yh_stride = r->out_n[SDR_RX_O_RDS_RES_I];
-      J.R = r->R;
-      J.tiles = (int)ceil_div(r->R, CR_TO);
-      J.nstreams = S;
-      const int64_t grid = (int64_t)J.tiles * S + S;
-      if (grid > 0x7fffffff || r->zlen[Z_ANTI_I] != J.zs) return fail(SDR_EINVAL, "sdr_rx: composite RDS geometry");
-      // spans: the matrix-core form (per job length, as launch_stage decides: a stream's outputs
-      // do not depend on how many streams share the launch)
-      if (M >= (int64_t)MM_MIN_WIN * MM_WT && M % 4 == 0 && J.nco.theta != nullptr) {
-        const int64_t wins = ceil_div(r->R, CM_WO) * S;
-        const int wgs = (int)std::min<int64_t>(CM_WGS, ceil_div(wins, 4));
-        if (J.nco.th32)
-          hipLaunchKernelGGL(rx_cresmm_kernel<true>, dim3((unsigned)(S + wgs)), dim3(RX_NT), 0, st, J, r->ctaps + CR_NTAPS, wgs);
-        else
-          hipLaunchKernelGGL(rx_cresmm_kernel<false>, dim3((unsigned)(S + wgs)), dim3(RX_NT), 0, st, J, r->ctaps + CR_NTAPS, wgs);
-      } else {
-        hipLaunchKernelGGL(rx_cres_kernel, dim3((unsigned)grid), dim3(CR_NT), 0, st, J);
-      }
-      HIP_TRY(hipGetLastError());
+  HIP_TRY(mark(r, 1 + SDR_RX_ST_C, st));
+  if (pl.rd) {
+    if (pl.cres) {
+      TRY(rx_cres(b));
     } else {
       // stage D: rational resamplers (fmRDSblock.py:184-199)
       std::vector<StageJob> Dj;
       for (int k = 0; k < 2; ++k) {
-        StageJob j = fir(SDR_RX_F_RDS_ANTI, k ? Z_ANTI_Q : Z_ANTI_I, o[k ? SDR_RX_O_RDS_LPF_Q : SDR_RX_O_RDS_LPF_I], M, ms,
-                         o[k ? SDR_RX_O_RDS_RES_Q : SDR_RX_O_RDS_RES_I], rs, r->rds_down);
+        StageJob j = fir(b, SDR_RX_F_RDS_ANTI, k ? Z_ANTI_Q : Z_ANTI_I, k ? SDR_RX_O_RDS_LPF_Q : SDR_RX_O_RDS_LPF_I, M,
+                         k ? SDR_RX_O_RDS_RES_Q : SDR_RX_O_RDS_RES_I, r->rds_down);
         j.kind = JK_RESAMPLE;
         j.U = r->rds_up;
         Dj.push_back(j);
       }
       HIP_TRY(launch_stage(Dj, S, st));
     }
-    HIP_TRY(mark(1 + SDR_RX_ST_D, st));
+    HIP_TRY(mark(r, 1 + SDR_RX_ST_D, st));
     // stage E: RRC (fmRDSblock.py:202-204)
-    HIP_TRY(launch_stage({fir(SDR_RX_F_RDS_RRC, Z_RRC_I, o[SDR_RX_O_RDS_RES_I], r->R, rs, o[SDR_RX_O_RDS_RRC_I], rs, 1),
-                          fir(SDR_RX_F_RDS_RRC, Z_RRC_Q, o[SDR_RX_O_RDS_RES_Q], r->R, rs, o[SDR_RX_O_RDS_RRC_Q], rs, 1)},
-                         S, st));
+    HIP_TRY(launch_stage({fir(b, SDR_RX_F_RDS_RRC, Z_RRC_I, SDR_RX_O_RDS_RES_I, r->R, SDR_RX_O_RDS_RRC_I, 1),
+                          fir(b, SDR_RX_F_RDS_RRC, Z_RRC_Q, SDR_RX_O_RDS_RES_Q, r->R, SDR_RX_O_RDS_RRC_Q, 1)}, S, st));
   } else {
-    HIP_TRY(mark(1 + SDR_RX_ST_D, st));
+    HIP_TRY(mark(r, 1 + SDR_RX_ST_D, st));
   }
   // the audio output stage (audio.hip): de-emphasis of L / R (mono without SDR_RX_STEREO) into
   // their _DE rows and the interleaved PCM, and of a stereo receiver's mono row when it is kept
-  const bool de_mono = r->de_on && stx && kept(SDR_RX_O_AUDIO_DE);
   if (r->de_on) {
-    TRY(sdr_audio_out_dev(c, o[stx ? SDR_RX_O_LEFT : SDR_RX_O_AUDIO], stx ? o[SDR_RX_O_RIGHT] : nullptr, r->A, as, S,
+    const bool stx = pl.stx;
+    const int64_t as = r->out_stride[SDR_RX_O_AUDIO];
+    TRY(sdr_audio_out_dev(r->c, o[stx ? SDR_RX_O_LEFT : SDR_RX_O_AUDIO], stx ? o[SDR_RX_O_RIGHT] : nullptr, r->A, as, S,
                           r->de_b, r->de_a1, r->de_state, o[stx ? SDR_RX_O_LEFT_DE : SDR_RX_O_AUDIO_DE],
-                          stx ? o[SDR_RX_O_RIGHT_DE] : nullptr, r->pcms[q], r->pcm_stride));
-    if (de_mono)
-      TRY(sdr_iir1_dev(c, o[SDR_RX_O_AUDIO], r->A, as, S, r->de_b, r->de_a1, r->de_mono, r->de_mono,
+                          stx ? o[SDR_RX_O_RIGHT_DE] : nullptr, r->pcms[b.q], r->pcm_stride));
+    if (b.de_mono)
+      TRY(sdr_iir1_dev(r->c, o[SDR_RX_O_AUDIO], r->A, as, S, r->de_b, r->de_a1, r->de_mono, r->de_mono,
                        o[SDR_RX_O_AUDIO_DE], as));
-    r->pcm = r->pcms[q];
+    r->pcm = r->pcms[b.q];
   }
-  for (int oo = 0; oo < SDR_RX_NOUTPUTS; ++oo) {
-    const bool nco_o = oo == SDR_RX_O_STEREO_NCO || oo == SDR_RX_O_RDS_NCO_I || oo == SDR_RX_O_RDS_NCO_Q;
-    const bool lpf_o = oo == SDR_RX_O_RDS_LPF_I || oo == SDR_RX_O_RDS_LPF_Q;
-    const bool pin_o = oo == SDR_RX_O_BPF_RECOVERY || oo == SDR_RX_O_RDS_PRE_PLL;      // (codes: when kept)
-    r->made[oo] = need_out(r, oo) && (!nco_o || nco_rows) && (!lpf_o || lpf_rows) && (!pin_o || !codes || kept(oo)) &&
-                  (oo != SDR_RX_O_AUDIO_DE || !stx || de_mono);
-  }
-  HIP_TRY(mark(1 + SDR_RX_ST_E, st));
-  if (r->pipe) HIP_TRY(hipEventRecord(r->ev_back[q], st));
-  std::memcpy(r->out, r->outs[q], sizeof r->out);
+  HIP_TRY(mark(r, 1 + SDR_RX_ST_E, st));
+  return SDR_OK;
+}
+
+}  // namespace
+
+int sdr_rx_process_dev(sdr_rx* r, const void* iq, int64_t iq_stride) {
+  if (r == nullptr) return fail(SDR_EINVAL, "sdr_rx is NULL");
+  if (iq == nullptr) return fail(SDR_EINVAL, "sdr_rx_process_dev: iq is NULL");
+  if (r->S > 1 && iq_stride < r->B) return fail(SDR_EINVAL, "sdr_rx_process_dev: iq_stride %lld < block", (long long)iq_stride);
+  if (!r->ready) TRY(rx_finalize(r));
+  TRY(set_dev(r->c));
+  const RxPlan& pl = r->plan;
+  RxBlock b{};
+  b.r = r;
+  b.q = r->pipe ? (int)(r->blocks % r->nq) : 0;
+  b.o = r->outs[b.q];
+  b.zi = r->bank[r->parity]; b.zf = r->bank[r->parity ^ 1];
+  const int Trf = (int)r->taps[SDR_RX_F_RF].size();
+  const int64_t xs = r->S > 1 ? iq_stride : r->B;
+  const bool fast = (Trf == 101 || Trf == 151) && r->rf_decim == 10 && (r->S <= 1 || r->u8 || xs % (r->u8 ? 8 : 2) == 0) &&
+                    ((uintptr_t)iq % (r->u8 ? 4 : 16)) == 0;
+  b.st = r->c->stream;
+  b.fs = (r->pipe && fast) ? r->front : b.st;
+  for (int f = 0; f < SDR_RX_NFILTERS; ++f)
+    if (filter_used(r, f)) TRY(get_taps(r->c, r->taps[f].data(), (int)r->taps[f].size(), &b.ts[f]));
+  b.ms = r->out_stride[SDR_RX_O_DEMOD];
+  b.nco_rows = (pl.stx && kept(r, SDR_RX_O_STEREO_NCO)) || (pl.rd && (kept(r, SDR_RX_O_RDS_NCO_I) || kept(r, SDR_RX_O_RDS_NCO_Q))) ||
+               r->M < 2 || (pl.rd && !pl.cres) || !pl.tiles_ok;
+  b.lpf_rows = pl.rd && (!pl.cres || kept(r, SDR_RX_O_RDS_LPF_I) || kept(r, SDR_RX_O_RDS_LPF_Q));
+  b.de_mono = r->de_on && pl.stx && kept(r, SDR_RX_O_AUDIO_DE);
+  b.c8 = pl.codes ? r->pcode + (int64_t)b.q * 2 * r->S * r->pcs : nullptr;
+  TRY(rx_front(b, iq, xs, fast));
+  TRY(rx_pll(b));
+  TRY(rx_back(b));
+  rx_made(b);
+  if (r->pipe) HIP_TRY(hipEventRecord(r->ev_back[b.q], b.st));
+  std::memcpy(r->out, r->outs[b.q], sizeof r->out);
   r->parity ^= 1;
   ++r->blocks;
   return SDR_OK;
@@ -2592,7 +2661,6 @@ bool stage_output(int o) {
          o != SDR_RX_O_AUDIO_DE && o != SDR_RX_O_LEFT_DE && o != SDR_RX_O_RIGHT_DE;   // (the audio output stage)
 }
 
-// Deliver the block in flight: wait for it, copy its rows out of pinned memory.
 // the oldest block in flight: wait for it, copy its outputs out of its pinned slot
 int deliver(sdr_rx* r) {
   if (r->pq_n == 0) return SDR_OK;

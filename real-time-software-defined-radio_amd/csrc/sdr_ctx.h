@@ -23,14 +23,16 @@ enum Slot {
 struct TapSet {
   std::vector<double> b;
   TapsF32 h;
+  bool sym = false;           // T <= SDR_MAX_TAPS and the f32 taps mirror-equal (linear phase: every firwin design)
   float* dev_f32 = nullptr;   // [0, cap): the taps; then, from dev_rev - 1: 0, the taps reversed, 0, 0
   float* dev_rev = nullptr;   // dev_rev[j] = h[T-1-j], dev_rev[-1] = dev_rev[T] = 0 (packed FIR tiles)
   double* dev_f64 = nullptr;
   int* dev_afr = nullptr;     // T = 101 / 151: the u8 MFMA front end's A fragments (fe_mfma.hip)
 };
 
-// a PLL loop's response table on the device (sdr_pll_resp_table), per (Kp, Ki, pseudo-block length)
-struct RespTable {
+// a PLL loop's table on the device: the response table (sdr_pll_resp_table) per (Kp, Ki,
+// pseudo-block length), or the solve's matrix powers (qtab_host) per (Kp, Ki) with pb = 0
+struct PllTable {
   double kp = 0.0, ki = 0.0;
   int64_t pb = 0;
   double* dev = nullptr;
@@ -56,8 +58,9 @@ struct sdr_ctx {
   // is spliced to the back and an overflow evicts the front, so no pointer handed out by
   // a lookup is invalidated by the other lookups of the same entry point (<= 4 per call).
   std::list<sdrint::TapSet> taps;
-  // PLL response tables of the long calls made on the context (a few loops; never evicted)
-  std::list<sdrint::RespTable> resp;
+  // PLL response tables of the long calls made on the context, and the matrix-power tables of
+  // its long and spec-only calls: least recently used first, bounded like the tap sets
+  std::list<sdrint::PllTable> resp, qtab;
   // pole-power tables of the first-order sections run on the context (a few; never evicted)
   std::list<sdrint::IirTab> iir;
   // PLL solve counters (SDR_PLL_NSTATS, device; sdr_pll_stats): every PLL launch of the
@@ -81,6 +84,8 @@ int get_resp(sdr_ctx* c, const PllCfg& cfg, int64_t n, const double** out);
 inline const float* resp32_of(const double* resp, int64_t pb) {
   return resp != nullptr ? reinterpret_cast<const float*>(resp + 2 * (pb + 5)) : nullptr;
 }
+// the device matrix-power table of loop cfg (PllJob::qtab; cached per context)
+int get_qtab(sdr_ctx* c, const PllCfg& cfg, const double** out);
 
 // the device pole-power table of a first-order section with denominator [1, a1] (cached per context)
 int get_iir_tab(sdr_ctx* c, double a1, const double** out);

@@ -100,7 +100,7 @@ struct PllJob {
   float* nco_i; float* nco_q; int64_t out_stride; PllCfg cfg; double* cbuf; int64_t c_stride;
   double off; int off_given;   // the prep kernel's trigOffset, when not read from state[5]
   const double* resp;          // long calls: the loop's response table (sdr_pll_resp_table), device
-  const double* qtab;          // the solve's matrix powers (pll.hip qtab_host); set by the launcher
+  const double* qtab;          // long and spec-only calls: the solve's matrix powers (qtab_host), device
   const int8_t* in8;           // nullable: the input as sign codes (sdr_nco.h pll_code), in8_stride bytes
   int64_t in8_stride;          //   apart per stream; read instead of `in` (long calls, spec-only calls)
   int th32;                    // long calls: the phase rows in the compact form (sdr_nco.h "compact
@@ -134,6 +134,8 @@ bool sdr_pll_long_geom(int64_t n, int64_t* pb, int* nb);
 // the loop's response table for a long call of n steps: 2 (pb + 1) doubles, row 0 of A^j for
 // j = 0 .. pb (sdr_nco.h); empty when n is not a long call
 void sdr_pll_resp_table(const PllCfg& c, int64_t n, std::vector<double>* out);
+// the solve's matrix-power table of loop c (host; the same size for every call length)
+void qtab_host(const PllCfg& c, std::vector<double>* out);
 // prep (per-sample constants) -> loop (one lane per recurrence) -> NCO; the three launches
 // separately (the receiver puts them on different streams) or together
 hipError_t sdr_launch_pll_prep(const PllJobs& jobs, hipStream_t st);

@@ -1,8 +1,8 @@
 #!/bin/bash
-# A/B of a diagnostic libsdr build (tools/build_dbg.sh) against the shipped one on one box:
+# A/B of another libsdr build (tools/build_dbg.sh, or another commit's library) against the shipped one on one box:
 # bench.py with the same args, interleaved, each run under its own time limit; the chain stops
 # at the first failure (set -e), nothing is retried.
-#   tools/ab_lib.sh <out-dir> <libsdr_X.so> <reps> <bench args, commas for spaces>
+#   tools/ab_dbg.sh <out-dir> <libsdr_X.so> <reps> <bench args, commas for spaces>
 # -> <out-dir>/{base,alt}_<i>.json
 set -e
 R=${GRAFT_REPO_ROOT:-$(pwd)}
@@ -15,4 +15,4 @@ for i in $(seq 1 "$N"); do
   SDR_LIB="$R/real-time-software-defined-radio_amd/$LIB" timeout -k 10 300 python -u bench.py $ARGS \
     > "$O/alt_$i.json" 2> "$O/alt_$i.err"
 done
-# (run r06/f: tools/ab_dbg.sh gpurun_out/th32 libsdr_th32.so 2 --workload,c5,--no-cpu)
+# (e.g. tools/ab_dbg.sh ab_tmp/c4 libsdr_parent.so 5 --workload,c4)

@@ -1,6 +1,9 @@
-# Diagnostic build of libsdr (never shipped): libsdr_<name>.so with the given -D flags, e.g.
-#   bash tools/build_dbg.sh dbg -DSDR_PLL_SPEC_PROF
-# then run a script with SDR_LIB=real-time-software-defined-radio_amd/libsdr_dbg.so.
+# Another build of libsdr beside the shipped one (never shipped itself): libsdr_<name>.so from the
+# sources as they stand, with any extra compiler flags, e.g.
+#   bash tools/build_dbg.sh O2 -O2
+# then run a script with SDR_LIB=real-time-software-defined-radio_amd/libsdr_O2.so.  To compare
+# against another commit, build that commit's library from a clean export of it and copy it here
+# under such a name (tools/ab_dbg.sh, tools/rx_digest.py).
 set -e
 NAME=$1
 shift

@@ -135,6 +135,12 @@ int main() {
     PllJobs P{};
     P.njobs = 1; P.nstreams = S; P.n = n;
     P.j[0] = PllJob{din, n, dst, dth, n + 2, nco_i, nco_q, n + 1, cfg, cb, cst};
+    std::vector<double> qh;                          // the solve's matrix powers: the caller's to upload
+    qtab_host(cfg, &qh);
+    double* dq;
+    CK(hipMalloc(&dq, sizeof(double) * qh.size()));
+    CK(hipMemcpy(dq, qh.data(), sizeof(double) * qh.size(), hipMemcpyHostToDevice));
+    P.j[0].qtab = dq;
     float ms = 0, best = 1e9f;
     for (int r = 0; r < 3; ++r) { reset(); CK(sdr_launch_pll_jobs(P, 0)); }
     CK(hipDeviceSynchronize());
@@ -195,7 +201,7 @@ int main() {
       CK(hipFree(c2));
     }
     CK(hipFree(din)); CK(hipFree(dst)); CK(hipFree(dth)); CK(hipFree(dth2));
-    CK(hipFree(nco_i)); CK(hipFree(nco_q)); CK(hipFree(cb));
+    CK(hipFree(nco_i)); CK(hipFree(nco_q)); CK(hipFree(cb)); CK(hipFree(dq));
   }
   return 0;
 }
