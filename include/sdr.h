@@ -376,6 +376,42 @@ int sdr_rx_state(sdr_rx* rx, double* phase, double* pll_stereo, double* pll_rds)
 /* sdr_pll_stats of the receiver's context, after waiting for every block in flight */
 int sdr_rx_pll_stats(sdr_rx* rx, int64_t* out, int reset);
 
+/* ---- wideband channelizer (multi-channel digital down-converter) ---------------------
+ * One interleaved-IQ capture (f32, or u8 as (x-128)/128) in, nch rows of interleaved complex
+ * f32 at Fs/decim out, row c centred on freq[c]: per channel "mix down, lfilter(b, 1, .),
+ * [::decim]",
+ *   y_c[m] = sum_j b[j] x[m decim - j] exp(-i 2 pi phi_c(m decim - j)),
+ * with x zero before the stream start and carried across calls, and the oscillator an integer
+ * phase accumulator: inc_c = rint(freq[c] 2^32) mod 2^32, phi_c(k) = ((inc_c k) mod 2^32) / 2^32
+ * turns at absolute sample index k (counted from the last reset) -- exact at any stream
+ * position and across any split into calls.  The frequency used is signed(inc_c) / 2^32
+ * (sdr_ddc_freq).  The reference has no channelizer: it is an addition, the stage a wideband
+ * front end needs before `nstreams` receivers; the rows are laid out as sdr_rx_process_dev
+ * reads its input rows (out_stride = its iq_stride, in complex samples).
+ * One matrix-core GEMM launch per call for all channels (csrc/ddc.hip) plus the history
+ * update; the object keeps the last taps-1 input samples, so the input is read in place.
+ * Waves work on windows of SDR_DDC_WINDOW outputs (16 where 126 decim + 2 taps floats exceed
+ * the wave's staging memory).  Samples must be finite and below 65 504 in magnitude (f16
+ * operands).  sdr_ddc_process_dev: async; iq aligned to one complex sample (8 B f32, 2 B u8),
+ * out to 8 B; channel c's n/decim samples start at out + 2 c out_stride floats.
+ * SDR_EINVAL (before any device work): nch, taps, decim out of range, a non-finite tap or
+ * frequency, |freq| > 0.5, bad dtype, n < 1, n % decim != 0, out_stride < n/decim, a reset
+ * position that is negative or no multiple of decim.  No configuration inside the limits is
+ * unsupported, and there is no host fallback. */
+#define SDR_DDC_MAX_CH 64
+#define SDR_DDC_MAX_TAPS 256
+#define SDR_DDC_MAX_DECIM 64
+#define SDR_DDC_WINDOW 64
+typedef struct sdr_ddc sdr_ddc;
+int sdr_ddc_create(sdr_ctx* ctx, int nch, const double* freq /* [nch], cycles/sample, |f| <= 0.5 */,
+                   const double* b, int taps, int decim, int iq_dtype, sdr_ddc** out);
+void sdr_ddc_destroy(sdr_ddc* ddc);
+int sdr_ddc_freq(sdr_ddc* ddc, double* actual /* [nch]: signed(inc) / 2^32 */);
+int sdr_ddc_reset(sdr_ddc* ddc, int64_t position);   /* zero history; position >= 0, % decim == 0 */
+int sdr_ddc_position(sdr_ddc* ddc, int64_t* position);
+int sdr_ddc_process_dev(sdr_ddc* ddc, const void* iq, int64_t n, float* out, int64_t out_stride);
+int sdr_ddc_run(sdr_ddc* ddc, const void* iq_host, int64_t n, float* out_host, int64_t out_stride); /* sync */
+
 /* ---- spectral diagnostics -----------------------------------------
  * Bartlett PSD, model/fmSupportLib.py:66-140 (estimatePSD; the C++ src/fourier.cpp:36-110
  * advances sample and list positions by the same nfft/2 and is not the parity target):

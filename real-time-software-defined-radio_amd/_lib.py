@@ -117,6 +117,13 @@ SIGNATURES = {
     "sdr_rx_pll_stats": (_i32, [_vp, _vp, _i32]),
     "sdr_rx_set_timing": (_i32, [_vp, _i32]),
     "sdr_rx_stage_ms": (_i32, [_vp, _fp]),
+    "sdr_ddc_create": (_i32, [_vp, _i32, _dp, _dp, _i32, _i32, _i32, _c.POINTER(_vp)]),
+    "sdr_ddc_destroy": (None, [_vp]),
+    "sdr_ddc_freq": (_i32, [_vp, _dp]),
+    "sdr_ddc_reset": (_i32, [_vp, _i64]),
+    "sdr_ddc_position": (_i32, [_vp, _c.POINTER(_i64)]),
+    "sdr_ddc_process_dev": (_i32, [_vp, _vp, _i64, _vp, _i64]),
+    "sdr_ddc_run": (_i32, [_vp, _vp, _i64, _vp, _i64]),
     "sdr_rds_link_create": (_i32, [_c.POINTER(_vp)]),
     "sdr_rds_link_destroy": (None, [_vp]),
     "sdr_rds_link_set_resync": (_i32, [_vp, _i32]),

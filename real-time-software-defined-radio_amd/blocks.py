@@ -389,3 +389,118 @@ class RdsLinkLayer:
             self.close()
         except Exception:
             pass
+
+
+class Channelizer:
+    """One wideband IQ capture to `len(freqs_hz)` receiver streams on the GPU (sdr_ddc,
+    csrc/ddc.hip): per channel "mix down by freqs_hz[c], lfilter(taps, 1, .), [::decim]", all
+    channels in one matrix-core launch.  The reference has no channelizer; this is the stage in
+    front of a Receiver when one front end carries several stations.
+
+    freqs_hz: the channel centres relative to the capture's centre, |f| <= fs / 2.  The
+    oscillators are 32-bit integer phase accumulators on the absolute sample index (exact at
+    any stream position and across any split into calls): `freqs_hz` then reads the quantised
+    frequencies, a multiple of fs / 2^32 each.  taps: an array of real FIR taps, a tap count,
+    or None (design.channel_coeffs(decim, taps): firwin at the output Nyquist).  The filter
+    history and the stream position are carried from call to call; every call takes a
+    multiple of `decim` samples.
+
+    process(iq) takes interleaved IQ (2 n values, f32 or u8) or a complex array and returns
+    the (nch, n / decim) complex64 rows; process_dev works on device memory in place: row c
+    starts 2 c out_stride floats into `out_ptr` -- the layout Receiver.process_dev reads with
+    iq_stride = out_stride."""
+
+    MAX_CH, MAX_TAPS, MAX_DECIM = 64, 256, 64      # include/sdr.h SDR_DDC_MAX_*
+    WINDOW = 64                                    # outputs per wave window (SDR_DDC_WINDOW)
+
+    def __init__(self, freqs_hz, fs: float, decim: int, taps=None, iq_dtype=np.float32, ctx=None):
+        self.handle = None
+        fs, decim = float(fs), int(decim)
+        if not (np.isfinite(fs) and fs > 0):
+            raise ValueError("fs must be positive")
+        if not 1 <= decim <= self.MAX_DECIM:
+            raise ValueError(f"decim={decim} outside [1, {self.MAX_DECIM}]")
+        f = np.atleast_1d(np.asarray(freqs_hz, dtype=np.float64))
+        if f.ndim != 1 or not 1 <= len(f) <= self.MAX_CH:
+            raise ValueError(f"{f.shape} channel frequencies: 1..{self.MAX_CH} channels")
+        if not np.all(np.isfinite(f)) or np.any(np.abs(f / fs) > 0.5):
+            raise ValueError("channel frequencies must be finite and within [-fs/2, fs/2]")
+        if taps is None or np.ndim(taps) == 0:
+            taps = design.channel_coeffs(decim, taps)
+        b = np.ascontiguousarray(np.atleast_1d(np.asarray(taps)), dtype=np.float64)
+        if b.ndim != 1 or not 1 <= len(b) <= self.MAX_TAPS:
+            raise ValueError(f"{b.shape} taps: 1..{self.MAX_TAPS} real taps")
+        if not np.all(np.isfinite(b)):
+            raise ValueError("taps must be finite")
+        dt = np.dtype(iq_dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.uint8)):
+            raise ValueError(f"iq_dtype {dt}: float32 or uint8")
+        self.u8 = dt == np.uint8
+        self.fs, self.decim, self.taps, self.nch = fs, decim, b, len(f)
+        self.inc = [design.ddc_phase_inc(v / fs) for v in f]
+        self.ctx = ctx if ctx is not None else _lib.get_context()
+        self.lib = self.ctx.lib
+        nu = np.ascontiguousarray(f / fs)
+        h = ctypes.c_void_p()
+        check(self.lib.sdr_ddc_create(self.ctx.handle, self.nch, f64p(nu), f64p(b), len(b), decim,
+                                      SDR_IQ_U8 if self.u8 else SDR_IQ_F32, ctypes.byref(h)), "sdr_ddc_create")
+        self.handle = h
+
+    @property
+    def freqs_hz(self) -> np.ndarray:
+        """The frequencies in use (sdr_ddc_freq): signed(inc) / 2^32 x fs."""
+        nu = np.empty(self.nch)
+        check(self.lib.sdr_ddc_freq(self.handle, f64p(nu)), "sdr_ddc_freq")
+        return nu * self.fs
+
+    @property
+    def position(self) -> int:
+        """Input samples taken since the last reset (plus its position)."""
+        p = ctypes.c_int64()
+        check(self.lib.sdr_ddc_position(self.handle, ctypes.byref(p)), "sdr_ddc_position")
+        return p.value
+
+    def reset(self, position: int = 0):
+        """Zero the filter history and set the stream position (>= 0, a multiple of decim)."""
+        check(self.lib.sdr_ddc_reset(self.handle, int(position)), "sdr_ddc_reset")
+
+    def _check_n(self, n, out_stride=None):
+        if n < 1 or n % self.decim:
+            raise ValueError(f"n={n} must be >= 1 and a multiple of decim={self.decim}")
+        if out_stride is not None and out_stride < n // self.decim:
+            raise ValueError(f"out_stride={out_stride} < n/decim={n // self.decim}")
+
+    def process(self, iq) -> np.ndarray:
+        """n complex samples from the host (interleaved f32 / u8, or complex for an f32
+        object) -> (nch, n / decim) complex64, synchronous (sdr_ddc_run)."""
+        iq = np.asarray(iq)
+        if np.iscomplexobj(iq):
+            if self.u8:
+                raise ValueError("a uint8 channelizer takes interleaved uint8 IQ")
+            iq = np.ascontiguousarray(iq, dtype=np.complex64).view(np.float32)
+        iq = np.ascontiguousarray(iq, dtype=np.uint8 if self.u8 else np.float32)
+        if iq.ndim != 1 or iq.size % 2:
+            raise ValueError("expected a 1-D array of interleaved I, Q values")
+        n = iq.size // 2
+        self._check_n(n)
+        out = np.empty((self.nch, n // self.decim), dtype=np.complex64)
+        check(self.lib.sdr_ddc_run(self.handle, iq.ctypes.data, n, out.ctypes.data, n // self.decim), "sdr_ddc_run")
+        return out
+
+    def process_dev(self, iq_ptr: int, n: int, out_ptr: int, out_stride: int):
+        """n complex samples at device pointer iq_ptr -> rows of n / decim complex f32 at
+        out_ptr, out_stride complex samples apart; async on the context stream."""
+        n, out_stride = int(n), int(out_stride)
+        self._check_n(n, out_stride)
+        check(self.lib.sdr_ddc_process_dev(self.handle, iq_ptr, n, out_ptr, out_stride), "sdr_ddc_process_dev")
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.sdr_ddc_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "sdr_ctx.h"
+#include "sdr_mma.h"
 #include "sdr_nco.h"
 
 using namespace sdrint;
@@ -519,14 +520,10 @@ __device__ __forceinline__ void pair_tile(const StageJob* Jf, int s, int64_t til
 // stages its own MM_WT-output window (MM_WT + 16 + 32 (KS - 1) samples, hi and lo) into its own
 // LDS slice, runs its MFMAs, stores, and moves to its next window, whose samples it loaded
 // into registers while the MFMAs ran.  Persistent: each wave owns every nw-th window of its job.
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-typedef _Float16 h4v __attribute__((ext_vector_type(4)));
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-typedef float f4v __attribute__((ext_vector_type(4)));
+// (the f16 vector types, the hi / lo split and the buffer descriptor: sdr_mma.h)
 
 constexpr int MM_NB = 4;                          // 256-output column blocks per wave window
 constexpr int MM_WT = MM_NB * 256;                // outputs per wave window
-constexpr float MM_LO = 2048.f;                   // the lo parts' scale
 constexpr int MM_MIN_WIN = 32;                    // a row of fewer windows stays on the VALU tiles
 
 template <int T>
@@ -542,31 +539,6 @@ constexpr int MM_LU_MAX = MmaShape<151>::LU;
 constexpr int MM_TAPS_MAX = 3 * 151;
 template <int FMAX> constexpr int mm_waves_per_cu() { return FMAX == 1 ? 12 : 8; }   // the VGPR limit
 
-struct MmHL { _Float16 hi, lo; };
-__device__ __forceinline__ MmHL mm_split(float v) {
-  const _Float16 h = (_Float16)v;
-  return MmHL{h, (_Float16)((v - (float)h) * MM_LO)};
-}
-// four samples at once: v_cvt_pk_f16_f32 pairs, the residuals as packed f32 ops
-__device__ __forceinline__ void mm_split4(float4 x, h4v* hi, h4v* lo) {
-  const f2 a{x.x, x.y}, c{x.z, x.w};
-  const h2v ha = __builtin_convertvector(a, h2v), hc = __builtin_convertvector(c, h2v);
-  const f2 ra = (a - __builtin_convertvector(ha, f2)) * MM_LO, rc = (c - __builtin_convertvector(hc, f2)) * MM_LO;
-  const h2v la = __builtin_convertvector(ra, h2v), lc = __builtin_convertvector(rc, h2v);
-  *hi = h4v{ha.x, ha.y, hc.x, hc.y};
-  *lo = h4v{la.x, la.y, lc.x, lc.y};
-}
-
-// A buffer descriptor over bytes [p, p + bytes) from wave-uniform values (readfirstlane: the
-// compiler cannot prove a wave-id-derived address uniform and would wrap every access in a
-// waterfall loop).  Raw buffer accesses outside it read 0 / are dropped by the hardware.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mm_rsrc(const void* p, int64_t bytes) {
-  const uintptr_t a = (uintptr_t)p;
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-  const int nb = __builtin_amdgcn_readfirstlane((int)bytes);
-  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uintptr_t)hi << 32) | lo), 0, nb, 0x00020000);
-}
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
 
 // wave w of job group Jf: windows gw, gw + nw, ... of the job's (stream, window) list.  Every
 // global access is a raw buffer access (the range check zero-fills samples outside the row and

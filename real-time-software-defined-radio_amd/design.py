@@ -56,6 +56,34 @@ def deemphasis_coeffs(tau: float = 75e-6, fs: float = 48e3):
     return np.array([k / (1.0 + k), k / (1.0 + k)]), np.array([1.0, -(1.0 - k) / (1.0 + k)])
 
 
+def channel_coeffs(decim: int, taps=None) -> np.ndarray:
+    """The channelizer's low-pass (Channelizer, sdr_ddc): signal.firwin(taps or 8 * decim,
+    1.0 / decim) -- the cutoff at the output Nyquist; the receiver's own RF filter does the
+    selective work.  decim 1 decimates nothing and needs no filter: a unit impulse."""
+    decim = int(decim)
+    if decim < 1:
+        raise ValueError("decim must be >= 1")
+    taps = int(taps) if taps else 8 * decim
+    if decim == 1:
+        return np.eye(1, taps)[0]
+    return signal.firwin(taps, 1.0 / decim)
+
+
+def ddc_phase_inc(nu: float) -> int:
+    """The channelizer's phase increment for a frequency of nu cycles per sample
+    (|nu| <= 0.5): rint(nu 2^32) mod 2^32, as a Python int in [0, 2^32)."""
+    nu = float(nu)
+    if not (math.isfinite(nu) and abs(nu) <= 0.5):
+        raise ValueError(f"frequency {nu} cycles/sample is not a finite value in [-0.5, 0.5]")
+    return int(np.rint(nu * 4294967296.0)) % (1 << 32)
+
+
+def ddc_actual_freq(inc: int) -> float:
+    """The frequency a phase increment stands for, cycles per sample: signed(inc) / 2^32."""
+    inc = int(inc) % (1 << 32)
+    return (inc - (1 << 32) if inc >= (1 << 31) else inc) / 4294967296.0
+
+
 def firwin_lpf(taps: int, fc: float, fs: float) -> np.ndarray:
     """signal.firwin(taps, fc/(fs/2), window='hann') as at model/fmMonoBlock.py:43."""
     return signal.firwin(taps, fc / (fs / 2), window=("hann"))
