@@ -412,6 +412,42 @@ int sdr_ddc_position(sdr_ddc* ddc, int64_t* position);
 int sdr_ddc_process_dev(sdr_ddc* ddc, const void* iq, int64_t n, float* out, int64_t out_stride);
 int sdr_ddc_run(sdr_ddc* ddc, const void* iq_host, int64_t n, float* out_host, int64_t out_stride); /* sync */
 
+/* ---- polyphase filter bank (uniformly spaced channels) ---------------------------------
+ * The channelizer's companion for channels on a uniform grid: nbins bins across the capture,
+ * bin k centred on k / nbins cycles per sample (bins >= nbins/2 are the negative frequencies),
+ * nch of them selected (any order, repeats allowed), one real prototype filter b of `taps`
+ * taps, decimation decim (any: it need not divide nbins, nor nbins it).  Per channel
+ *   y_c[m] = sum_j b[j] x[m decim - j] exp(-2 pi i ((bin[c] (k mod nbins)) mod nbins) / nbins),
+ *   k = position + m decim - j,
+ * x zero before the stream start and carried across calls; the phase is integer arithmetic mod
+ * nbins -- exact at any stream position and across any split into calls.  Computed as a
+ * polyphase fold (the filter's MACs shared by all channels: `taps` real-by-complex MACs per
+ * output time) and an nbins-point DFT for the selected bins on the matrix cores, one launch
+ * per call (csrc/pfb.hip) plus the history update; the object keeps the last taps-1 input
+ * samples, so the input is read in place.  Workgroups work on windows of SDR_PFB_WINDOW output
+ * times (16 where the window's buffers exceed 80 KB of LDS).  Samples must be finite and
+ * sum|b| max|x| below 65 504 (f16 operands).  Row layout, alignment and the call-time rules are
+ * sdr_ddc_process_dev's: async; iq aligned to one complex sample (8 B f32, 2 B u8), out to 8 B;
+ * n >= 1, n % decim == 0, out_stride >= n/decim; channel c's n/decim samples start at
+ * out + 2 c out_stride floats -- the rows sdr_rx_process_dev reads.
+ * SDR_EINVAL (before any device work): nbins, nch, taps, decim out of range, a bin outside
+ * [0, nbins), a non-finite tap, bad dtype, NULL pointers, the call-time rules, a reset position
+ * that is negative or no multiple of decim.  No configuration inside the limits is unsupported,
+ * and there is no host fallback. */
+#define SDR_PFB_MAX_BINS 256
+#define SDR_PFB_MAX_CH 256
+#define SDR_PFB_MAX_TAPS 4096
+#define SDR_PFB_MAX_DECIM 64
+#define SDR_PFB_WINDOW 64
+typedef struct sdr_pfb sdr_pfb;
+int sdr_pfb_create(sdr_ctx* ctx, int nbins, int nch, const int* bin /* [nch], 0 <= bin < nbins */,
+                   const double* b, int taps, int decim, int iq_dtype, sdr_pfb** out);
+void sdr_pfb_destroy(sdr_pfb* pfb);
+int sdr_pfb_reset(sdr_pfb* pfb, int64_t position);   /* zero history; position >= 0, % decim == 0 */
+int sdr_pfb_position(sdr_pfb* pfb, int64_t* position);
+int sdr_pfb_process_dev(sdr_pfb* pfb, const void* iq, int64_t n, float* out, int64_t out_stride);
+int sdr_pfb_run(sdr_pfb* pfb, const void* iq_host, int64_t n, float* out_host, int64_t out_stride); /* sync */
+
 /* ---- spectral diagnostics -----------------------------------------
  * Bartlett PSD, model/fmSupportLib.py:66-140 (estimatePSD; the C++ src/fourier.cpp:36-110
  * advances sample and list positions by the same nfft/2 and is not the parity target):

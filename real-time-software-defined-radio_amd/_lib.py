@@ -124,6 +124,12 @@ SIGNATURES = {
     "sdr_ddc_position": (_i32, [_vp, _c.POINTER(_i64)]),
     "sdr_ddc_process_dev": (_i32, [_vp, _vp, _i64, _vp, _i64]),
     "sdr_ddc_run": (_i32, [_vp, _vp, _i64, _vp, _i64]),
+    "sdr_pfb_create": (_i32, [_vp, _i32, _i32, _c.POINTER(_i32), _dp, _i32, _i32, _i32, _c.POINTER(_vp)]),
+    "sdr_pfb_destroy": (None, [_vp]),
+    "sdr_pfb_reset": (_i32, [_vp, _i64]),
+    "sdr_pfb_position": (_i32, [_vp, _c.POINTER(_i64)]),
+    "sdr_pfb_process_dev": (_i32, [_vp, _vp, _i64, _vp, _i64]),
+    "sdr_pfb_run": (_i32, [_vp, _vp, _i64, _vp, _i64]),
     "sdr_rds_link_create": (_i32, [_c.POINTER(_vp)]),
     "sdr_rds_link_destroy": (None, [_vp]),
     "sdr_rds_link_set_resync": (_i32, [_vp, _i32]),

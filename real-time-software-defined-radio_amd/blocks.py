@@ -504,3 +504,131 @@ class Channelizer:
             self.close()
         except Exception:
             pass
+
+
+class FilterBank:
+    """A polyphase filter bank on the GPU (sdr_pfb, csrc/pfb.hip): one wideband IQ capture to
+    the selected bins of a uniform grid of `nbins` across the capture, bin k centred on
+    k / nbins x fs (bins >= nbins / 2 are the negative frequencies), each at fs / decim.  Per
+    channel it is Channelizer's "mix down, lfilter(taps, 1, .), [::decim]" with the oscillator
+    on the grid -- its phase ((bin k) mod nbins) / nbins turns at absolute sample index k, exact
+    integer arithmetic -- but the filter is folded once for all channels and only an
+    nbins-point DFT is per channel, so the channel count does not multiply the filter's work:
+    the front end for a whole band of uniformly spaced stations.
+
+    bins: the selected bins, in any order, repeats allowed, unsigned in [0, nbins) or signed in
+    [-nbins/2, nbins/2) (reduced mod nbins); None selects all of them in order.  taps: an array
+    of real prototype taps, a tap count, or None (design.pfb_coeffs(nbins): firwin at half the
+    bin spacing, 8 taps per bin).  decim is free: it need not divide nbins.  The filter history
+    and the stream position are carried from call to call; every call takes a multiple of
+    `decim` samples.
+
+    process / process_dev / reset / position / close are Channelizer's, the rows laid out the
+    same way: row c starts 2 c out_stride floats into `out_ptr`, what Receiver.process_dev reads
+    with iq_stride = out_stride."""
+
+    MAX_BINS, MAX_CH, MAX_TAPS, MAX_DECIM = 256, 256, 4096, 64      # include/sdr.h SDR_PFB_MAX_*
+    WINDOW = 64                                                     # output times per window (SDR_PFB_WINDOW)
+
+    def __init__(self, nbins: int, fs: float, decim: int, bins=None, taps=None, iq_dtype=np.float32, ctx=None):
+        self.handle = None
+        nbins, fs, decim = int(nbins), float(fs), int(decim)
+        if not (np.isfinite(fs) and fs > 0):
+            raise ValueError("fs must be positive")
+        if not 1 <= nbins <= self.MAX_BINS:
+            raise ValueError(f"nbins={nbins} outside [1, {self.MAX_BINS}]")
+        if not 1 <= decim <= self.MAX_DECIM:
+            raise ValueError(f"decim={decim} outside [1, {self.MAX_DECIM}]")
+        k = np.arange(nbins) if bins is None else np.atleast_1d(np.asarray(bins))
+        if k.ndim != 1 or not 1 <= len(k) <= self.MAX_CH:
+            raise ValueError(f"{k.shape} bins: 1..{self.MAX_CH} channels")
+        if not np.all(np.isfinite(k)) or np.any(k != np.rint(k)):
+            raise ValueError("bins must be integers")
+        k = k.astype(np.int64)
+        if np.any(2 * k < -nbins) or np.any(k >= nbins):
+            raise ValueError(f"bins must lie in [-nbins/2, nbins) with nbins={nbins}")
+        if taps is None or np.ndim(taps) == 0:
+            if taps is not None and not 1 <= int(taps) <= self.MAX_TAPS:
+                raise ValueError(f"taps={taps} outside [1, {self.MAX_TAPS}]")
+            if taps is None:
+                taps = design.pfb_coeffs(nbins)
+            else:                                   # a tap count: the same prototype at that length
+                taps = design.signal.firwin(int(taps), 1.0 / nbins) if nbins > 1 else np.eye(1, int(taps))[0]
+        b = np.ascontiguousarray(np.atleast_1d(np.asarray(taps)), dtype=np.float64)
+        if b.ndim != 1 or not 1 <= len(b) <= self.MAX_TAPS:
+            raise ValueError(f"{b.shape} taps: 1..{self.MAX_TAPS} real taps")
+        if not np.all(np.isfinite(b)):
+            raise ValueError("taps must be finite")
+        dt = np.dtype(iq_dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.uint8)):
+            raise ValueError(f"iq_dtype {dt}: float32 or uint8")
+        self.u8 = dt == np.uint8
+        self.nbins, self.fs, self.decim, self.taps = nbins, fs, decim, b
+        self.bins = np.ascontiguousarray(k % nbins, dtype=np.int32)
+        self.nch = len(self.bins)
+        self.ctx = ctx if ctx is not None else _lib.get_context()
+        self.lib = self.ctx.lib
+        h = ctypes.c_void_p()
+        check(self.lib.sdr_pfb_create(self.ctx.handle, nbins, self.nch, self.bins.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                      f64p(b), len(b), decim, SDR_IQ_U8 if self.u8 else SDR_IQ_F32, ctypes.byref(h)),
+              "sdr_pfb_create")
+        self.handle = h
+
+    @property
+    def freqs_hz(self) -> np.ndarray:
+        """The channel centres: signed(bin) / nbins x fs (bins >= nbins / 2 are negative)."""
+        k = self.bins.astype(np.int64)
+        return np.where(2 * k >= self.nbins, k - self.nbins, k) / self.nbins * self.fs
+
+    @property
+    def position(self) -> int:
+        """Input samples taken since the last reset (plus its position)."""
+        p = ctypes.c_int64()
+        check(self.lib.sdr_pfb_position(self.handle, ctypes.byref(p)), "sdr_pfb_position")
+        return p.value
+
+    def reset(self, position: int = 0):
+        """Zero the filter history and set the stream position (>= 0, a multiple of decim)."""
+        check(self.lib.sdr_pfb_reset(self.handle, int(position)), "sdr_pfb_reset")
+
+    def _check_n(self, n, out_stride=None):
+        if n < 1 or n % self.decim:
+            raise ValueError(f"n={n} must be >= 1 and a multiple of decim={self.decim}")
+        if out_stride is not None and out_stride < n // self.decim:
+            raise ValueError(f"out_stride={out_stride} < n/decim={n // self.decim}")
+
+    def process(self, iq) -> np.ndarray:
+        """n complex samples from the host (interleaved f32 / u8, or complex for an f32
+        object) -> (nch, n / decim) complex64, synchronous (sdr_pfb_run)."""
+        iq = np.asarray(iq)
+        if np.iscomplexobj(iq):
+            if self.u8:
+                raise ValueError("a uint8 filter bank takes interleaved uint8 IQ")
+            iq = np.ascontiguousarray(iq, dtype=np.complex64).view(np.float32)
+        iq = np.ascontiguousarray(iq, dtype=np.uint8 if self.u8 else np.float32)
+        if iq.ndim != 1 or iq.size % 2:
+            raise ValueError("expected a 1-D array of interleaved I, Q values")
+        n = iq.size // 2
+        self._check_n(n)
+        out = np.empty((self.nch, n // self.decim), dtype=np.complex64)
+        check(self.lib.sdr_pfb_run(self.handle, iq.ctypes.data, n, out.ctypes.data, n // self.decim), "sdr_pfb_run")
+        return out
+
+    def process_dev(self, iq_ptr: int, n: int, out_ptr: int, out_stride: int):
+        """n complex samples at device pointer iq_ptr -> rows of n / decim complex f32 at
+        out_ptr, out_stride complex samples apart; async on the context stream."""
+        n, out_stride = int(n), int(out_stride)
+        self._check_n(n, out_stride)
+        check(self.lib.sdr_pfb_process_dev(self.handle, iq_ptr, n, out_ptr, out_stride), "sdr_pfb_process_dev")
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.sdr_pfb_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+

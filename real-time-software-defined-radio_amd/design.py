@@ -69,6 +69,18 @@ def channel_coeffs(decim: int, taps=None) -> np.ndarray:
     return signal.firwin(taps, 1.0 / decim)
 
 
+def pfb_coeffs(nbins: int, taps_per_bin: int = 8) -> np.ndarray:
+    """The filter bank's prototype low-pass (FilterBank, sdr_pfb): signal.firwin(nbins *
+    taps_per_bin, 1.0 / nbins) -- the cutoff at half the bin spacing, in Nyquist units.  One bin
+    is the whole band and needs no filter: a unit impulse."""
+    nbins, taps_per_bin = int(nbins), int(taps_per_bin)
+    if nbins < 1 or taps_per_bin < 1:
+        raise ValueError("nbins and taps_per_bin must be >= 1")
+    if nbins == 1:
+        return np.eye(1, taps_per_bin)[0]
+    return signal.firwin(nbins * taps_per_bin, 1.0 / nbins)
+
+
 def ddc_phase_inc(nu: float) -> int:
     """The channelizer's phase increment for a frequency of nu cycles per sample
     (|nu| <= 0.5): rint(nu 2^32) mod 2^32, as a Python int in [0, 2^32)."""
