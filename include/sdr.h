@@ -492,6 +492,43 @@ int sdr_rds_link_block(sdr_rds_link* link, const double* rrc_i, int64_t n, int64
                        int64_t* n_symbols, uint8_t* bits, int64_t max_bits, int64_t* n_bits,
                        uint8_t* diff, int64_t max_diff, int64_t* n_diff);
 
+/* ---- RDS link layer on the device, for all streams of a call ---------------------------
+ * The same link layer (sdr_rds_link_block is its specification, quirks included) for `nstreams`
+ * rows of in-phase RRC output in device memory -- a receiver's "rrc_i" rows, read in place: row s
+ * starts s * stride floats into rrc_i.  Every stream's state (symbol offset, start position,
+ * front / previous bit, lone symbol, carried bits, positions, false-positive count, whether
+ * block 0 has run) lives in device memory; bits, scanned bits, events and state equal the host
+ * layer's, fed the same f32 samples widened to f64, call by call.  Three launches per call
+ * whatever nstreams and n are (csrc/rds.hip).
+ * sdr_rds_links_process_dev: async on the context stream; SDR_RDS_LINKS_MIN_N <= n <= max_n
+ * (below the minimum the host layer can fail part-way through a state update; from it on only
+ * on NaN), stride >= n; SDR_EINVAL before any device work otherwise.
+ * sdr_rds_links_events (synchronises): the last call's events, ev[nstreams][max_events][4] =
+ * {type 0..3 = A..D or SDR_RDS_RESYNC, position, accepted, word}, word = the window's 16
+ * information bits, the first one most significant (0 for a re-sync); n_events[s] is the true
+ * count -- beyond max_events the excess is dropped, the state still advances over every match
+ * and status[s] has SDR_RDS_LINKS_OVERFLOW.  Where the host layer returns its NaN error (a NaN
+ * among block 0's first 24 samples, or a last symbol that is NaN) status[s] has
+ * SDR_RDS_LINKS_FAULT, the stream emits nothing and keeps its state, as the host layer does;
+ * the other streams are unaffected.  NaN anywhere else compares false, as on the host.
+ * sdr_rds_links_bits (synchronises): the last call's Manchester bits and scanned row (carried
+ * bits first) of one stream, one byte per bit; either buffer may be NULL. */
+#define SDR_RDS_LINKS_MIN_N 1536
+#define SDR_RDS_LINKS_MAX_N (1 << 30)
+#define SDR_RDS_LINKS_MAX_STREAMS 65535
+#define SDR_RDS_LINKS_MAX_EVENTS (1 << 20)
+#define SDR_RDS_LINKS_FAULT 1
+#define SDR_RDS_LINKS_OVERFLOW 2
+typedef struct sdr_rds_links sdr_rds_links;
+int sdr_rds_links_create(sdr_ctx* ctx, int nstreams, int64_t max_n, int64_t max_events, sdr_rds_links** out);
+void sdr_rds_links_destroy(sdr_rds_links* links);
+int sdr_rds_links_set_resync(sdr_rds_links* links, int after_bad_syncs);   /* as sdr_rds_link_set_resync */
+int sdr_rds_links_reset(sdr_rds_links* links);                             /* every stream back to block 0 */
+int sdr_rds_links_process_dev(sdr_rds_links* links, const float* rrc_i, int64_t n, int64_t stride);
+int sdr_rds_links_events(sdr_rds_links* links, int64_t* ev, int64_t* n_events, int32_t* status);
+int sdr_rds_links_bits(sdr_rds_links* links, int stream, uint8_t* bits, int64_t max_bits, int64_t* n_bits,
+                       uint8_t* diff, int64_t max_diff, int64_t* n_diff);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,8 @@ RX_OUTPUTS = ("demod", "audio", "bpf_recovery", "nco", "bpf_extraction", "stereo
 # LPF + x19/80 resampler (the composite filter, csrc/rx.hip rx_cres_kernel)
 RX_STAGES = ("fe", "filters_of_demod", "rds_square", "pll", "mix_lpf", "resample", "rrc")
 # PLL solve counters (include/sdr.h SDR_PLL_ST_*)
+# device-side RDS link layer (include/sdr.h sdr_rds_links_*)
+SDR_RDS_LINKS_MIN_N, SDR_RDS_LINKS_FAULT, SDR_RDS_LINKS_OVERFLOW = 1536, 1, 2
 PLL_STATS = ("recurrences", "spec_r0", "spec_r1", "spec_r2", "sequential", "long_guessed", "long_chained",
              "long_maxgap", "long_stops", "long_tail", "long_linear")
 
@@ -135,6 +137,13 @@ SIGNATURES = {
     "sdr_rds_link_set_resync": (_i32, [_vp, _i32]),
     "sdr_rds_link_block": (_i32, [_vp, _dp, _i64, _vp, _i64, _c.POINTER(_i64), _vp, _i64, _c.POINTER(_i64),
                                   _vp, _i64, _c.POINTER(_i64), _vp, _i64, _c.POINTER(_i64)]),
+    "sdr_rds_links_create": (_i32, [_vp, _i32, _i64, _i64, _c.POINTER(_vp)]),
+    "sdr_rds_links_destroy": (None, [_vp]),
+    "sdr_rds_links_set_resync": (_i32, [_vp, _i32]),
+    "sdr_rds_links_reset": (_i32, [_vp]),
+    "sdr_rds_links_process_dev": (_i32, [_vp, _vp, _i64, _i64]),
+    "sdr_rds_links_events": (_i32, [_vp, _vp, _vp, _vp]),
+    "sdr_rds_links_bits": (_i32, [_vp, _i32, _vp, _i64, _c.POINTER(_i64), _vp, _i64, _c.POINTER(_i64)]),
 }
 
 _lib = None

@@ -238,6 +238,15 @@ class Receiver:
         check(self.lib.sdr_rx_reset(self.handle), "sdr_rx_reset")
         self._pending.clear()
 
+    def rds_link(self, **kw) -> "RdsLinkBank":
+        """A device-side RDS link layer sized to this receiver (RdsLinkBank: one stream per
+        receiver stream, rows of the "rrc_i" length); feed it with bank.process_rx(receiver)
+        after each block.  Needs rds=True."""
+        if not self.flags & SDR_RX_RDS:
+            raise ValueError("rds_link needs a receiver with rds=True")
+        kw.setdefault("ctx", self.ctx)
+        return RdsLinkBank(self.S, self._length("rrc_i"), **kw)
+
     def set_timing(self, on: bool = True):
         """Record HIP events between the receiver's launches (stage_ms)."""
         check(self.lib.sdr_rx_set_timing(self.handle, int(bool(on))), "sdr_rx_set_timing")
@@ -389,6 +398,106 @@ class RdsLinkLayer:
             self.close()
         except Exception:
             pass
+
+
+class RdsLinkBank:
+    """RdsLinkLayer for `nstreams` streams at once, on the GPU (sdr_rds_links, csrc/rds.hip): the
+    in-phase RRC rows are read where the receiver left them, every stream's link state stays in
+    device memory, and what comes back is the events -- per stream a list of
+    (type, position, accepted, word), the first three as RdsLinkLayer reports them and `word` the
+    block's 16 information bits (0 for a RESYNC).  Bits, scanned bits, events and state equal
+    RdsLinkLayer's on the same float32 samples, call by call.
+
+    max_n: the longest row a call may bring (a call takes MIN_N <= n <= max_n samples per row).
+    max_events: events kept per stream and call (default: two per window -- no call can give more
+    -- up to 4096); beyond it the excess is dropped, `counts` still has the true number and
+    `status` OVERFLOW.
+    resync_after: as RdsLinkLayer's."""
+
+    TYPES = "ABCD"
+    RESYNC = 4
+    MIN_N = _lib.SDR_RDS_LINKS_MIN_N
+    FAULT, OVERFLOW = _lib.SDR_RDS_LINKS_FAULT, _lib.SDR_RDS_LINKS_OVERFLOW
+
+    def __init__(self, nstreams: int, max_n: int, *, max_events=None, resync_after: int = 0, ctx=None):
+        self.handle = None
+        self.S, self.max_n = int(nstreams), int(max_n)
+        # a call scans at most (max_n / 24) / 2 + 2 windows, and a window gives at most two events
+        self.max_events = int(max_events) if max_events is not None else min(2 * (self.max_n // 48 + 4), 4096)
+        self.ctx = ctx if ctx is not None else _lib.get_context()
+        self.lib = self.ctx.lib
+        h = ctypes.c_void_p()
+        check(self.lib.sdr_rds_links_create(self.ctx.handle, self.S, self.max_n, self.max_events, ctypes.byref(h)),
+              "sdr_rds_links_create")
+        self.handle = h
+        self.counts = np.zeros(self.S, dtype=np.int64)
+        if resync_after:
+            self.set_resync(resync_after)
+
+    def set_resync(self, after_bad_syncs: int):
+        check(self.lib.sdr_rds_links_set_resync(self.handle, int(after_bad_syncs)), "sdr_rds_links_set_resync")
+
+    def process_dev(self, ptr: int, n: int, stride: int):
+        """One call for every stream: row s is the n floats at device pointer ptr + 4 s stride.
+        Async on the context stream."""
+        check(self.lib.sdr_rds_links_process_dev(self.handle, ptr, int(n), int(stride)), "sdr_rds_links_process_dev")
+
+    def process_rx(self, receiver: "Receiver"):
+        """The receiver's latest "rrc_i" rows (looked up at every call: a pipelined receiver
+        alternates its row sets)."""
+        if receiver.S != self.S:
+            raise ValueError(f"the receiver has {receiver.S} streams, the bank {self.S}")
+        ptr, stride, n = receiver.output_ptr("rrc_i")
+        self.process_dev(ptr, n, stride)
+
+    def events(self):
+        """(events, status) of the last call, after waiting for it: events[s] the stream's list of
+        (type, position, accepted, word), status[s] 0 or FAULT / OVERFLOW bits; `counts` is set
+        to the true event counts."""
+        ev = np.zeros((self.S, self.max_events, 4), dtype=np.int64)
+        ne = np.zeros(self.S, dtype=np.int64)
+        status = np.zeros(self.S, dtype=np.int32)
+        check(self.lib.sdr_rds_links_events(self.handle, ev.ctypes.data, ne.ctypes.data, status.ctypes.data),
+              "sdr_rds_links_events")
+        self.counts = ne
+        return [[tuple(e) for e in ev[s, :min(int(ne[s]), self.max_events)].tolist()] for s in range(self.S)], status
+
+    def bits(self, stream: int):
+        """(bits, diff) of the last call for one stream: the Manchester bits and the scanned row
+        (carried bits first), uint8 -- RdsLinkLayer's 'bits' and 'diff'."""
+        nb_max = self.max_n // 48 + 2
+        bits, diff = np.empty(nb_max, dtype=np.uint8), np.empty(nb_max + 32, dtype=np.uint8)
+        nb, nd = ctypes.c_int64(), ctypes.c_int64()
+        check(self.lib.sdr_rds_links_bits(self.handle, int(stream), bits.ctypes.data, len(bits), ctypes.byref(nb),
+                                          diff.ctypes.data, len(diff), ctypes.byref(nd)), "sdr_rds_links_bits")
+        return bits[:nb.value].copy(), diff[:nd.value].copy()
+
+    def reset(self):
+        """Every stream back to block 0."""
+        check(self.lib.sdr_rds_links_reset(self.handle), "sdr_rds_links_reset")
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.sdr_rds_links_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def rds_groups(events):
+    """One stream's events -> the groups in them: an accepted A at position p with accepted B, C,
+    D at p + 26, p + 52, p + 78 gives (pi, b, c, d), the four blocks' information words.  Takes
+    the 4-tuples of RdsLinkBank.events()."""
+    ok = {(int(e[1]), int(e[0])): int(e[3]) for e in events if len(e) >= 4 and e[2] and 0 <= e[0] < 4}
+    groups = []
+    for (p, t) in sorted(ok):
+        if t == 0 and all((p + 26 * k, k) in ok for k in (1, 2, 3)):
+            groups.append(tuple(ok[(p + 26 * k, k)] for k in range(4)))
+    return groups
 
 
 class Channelizer:
