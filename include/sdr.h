@@ -448,6 +448,48 @@ int sdr_pfb_position(sdr_pfb* pfb, int64_t* position);
 int sdr_pfb_process_dev(sdr_pfb* pfb, const void* iq, int64_t n, float* out, int64_t out_stride);
 int sdr_pfb_run(sdr_pfb* pfb, const void* iq_host, int64_t n, float* out_host, int64_t out_stride); /* sync */
 
+/* ---- wideband spectrum / waterfall ---------------------------------------------------------
+ * Welch periodogram rows of one interleaved-IQ capture in device memory (f32, or u8 as
+ * (x - 128) / 128) -- the buffer sdr_ddc_process_dev / sdr_pfb_process_dev read, in place: where
+ * are the stations?  With segment s starting at sample s hop, s = 0 .. nseg - 1,
+ * nseg = (n - nfft) / hop + 1, and the window w,
+ *   X_s[k]    = sum_{i < nfft} w[i] x[s hop + i] exp(-2 pi i k i / nfft)
+ *   out[r][j] = (1 / (navg (sum w)^2)) sum_{s in [r navg, (r + 1) navg)} |X_s[k]|^2,
+ *   k = (j + nfft / 2) mod nfft
+ * linear power in f32, bin j centred on (j - nfft / 2) fs / nfft (ascending, as a waterfall row
+ * and np.fft.fftshift).  navg = 0: one row of all nseg segments.  rows = nseg / navg; trailing
+ * segments that do not fill a row are ignored.  For hop <= nfft this is scipy.signal.spectrogram(
+ * x, window=w, nperseg=nfft, noverlap=nfft-hop, detrend=False, return_onesided=False,
+ * scaling='spectrum', mode='psd') averaged over groups of navg columns and shifted; hop > nfft
+ * (a sparse monitor) skips samples.  Stateless: nothing is carried between calls.
+ * nfft: a power of two in [SDR_SPEC_MIN_NFFT, SDR_SPEC_MAX_NFFT]; hop: 1 .. SDR_SPEC_MAX_HOP,
+ * odd or even; navg: 0 or >= 1; window: nfft finite values of any sign with a non-zero sum, NULL
+ * for the periodic Hann window 0.5 - 0.5 cos(2 pi i / nfft).
+ * An f32 FFT on the device (csrc/spectrum.hip): radix-16 / 8 butterflies in registers, the turns
+ * from a table computed in f64 on the host.  A workgroup takes a chunk of consecutive segments
+ * of one row and adds their |X|^2 in a fixed order; a row of more than SDR_SPEC_SPLIT_SEGS
+ * segments may be cut into several chunks (the call into about 2 048, none shorter than
+ * SDR_SPEC_SPLIT_SEGS), whose sums a second launch adds in chunk order: no atomics, the same call
+ * gives the same bits.  A non-finite sample makes every bin of its row NaN, and no other row.
+ * sdr_spec_rows: host arithmetic only.  sdr_spec_process_dev: async; iq aligned to one complex
+ * sample (8 B f32, 2 B u8), out to 4 B; row r starts r out_stride floats into out, and the
+ * out_stride - nfft floats between rows are not written.  All sample offsets are 64-bit.
+ * SDR_EINVAL (before any device work): nfft no power of two or out of range, hop or navg out of
+ * range, a non-finite window value, a window that sums to zero, bad dtype, NULL pointers,
+ * n < nfft, an n that yields no complete row, out_stride < nfft.  No configuration inside the
+ * limits is unsupported, and there is no host fallback. */
+#define SDR_SPEC_MIN_NFFT 64
+#define SDR_SPEC_MAX_NFFT 8192
+#define SDR_SPEC_MAX_HOP  (1 << 24)
+#define SDR_SPEC_SPLIT_SEGS 8
+typedef struct sdr_spec sdr_spec;
+int  sdr_spec_create(sdr_ctx* ctx, int nfft, const double* window /* [nfft]; NULL = periodic Hann */,
+                     int64_t hop, int64_t navg, int iq_dtype, sdr_spec** out);
+void sdr_spec_destroy(sdr_spec* spec);
+int  sdr_spec_rows(sdr_spec* spec, int64_t n, int64_t* nseg, int64_t* rows);      /* host arithmetic only */
+int  sdr_spec_process_dev(sdr_spec* spec, const void* iq, int64_t n, float* out, int64_t out_stride); /* async */
+int  sdr_spec_run(sdr_spec* spec, const void* iq_host, int64_t n, float* out_host, int64_t out_stride); /* sync */
+
 /* ---- spectral diagnostics -----------------------------------------
  * Bartlett PSD, model/fmSupportLib.py:66-140 (estimatePSD; the C++ src/fourier.cpp:36-110
  * advances sample and list positions by the same nfft/2 and is not the parity target):

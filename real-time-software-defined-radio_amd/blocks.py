@@ -741,3 +741,174 @@ class FilterBank:
         except Exception:
             pass
 
+
+
+def spectrum_rows(n: int, nfft: int, hop: int, navg: int):
+    """(nseg, rows) of a Spectrum call of n samples: nseg = (n - nfft) // hop + 1 segments,
+    rows = nseg // navg (navg = 0: one row of all of them).  Host arithmetic (sdr_spec_rows)."""
+    n, nfft, hop, navg = int(n), int(nfft), int(hop), int(navg)
+    if n < nfft:
+        raise ValueError(f"n={n} < nfft={nfft}")
+    nseg = (n - nfft) // hop + 1
+    rows = nseg // navg if navg > 0 else 1
+    if rows < 1:
+        raise ValueError(f"n={n} yields {nseg} segments, no complete row of navg={navg}")
+    return nseg, rows
+
+
+class Spectrum:
+    """The spectrum / waterfall of a wideband IQ capture on the GPU (sdr_spec, csrc/spectrum.hip):
+    Welch periodogram rows of the buffer Channelizer / FilterBank read, in place -- which of the
+    band's channels carry a station?  With segment s starting at sample s hop and window w,
+
+        X_s[k]    = sum_{i < nfft} w[i] x[s hop + i] exp(-2 pi i k i / nfft)
+        out[r][j] = (1 / (navg (sum w)^2)) sum_{s in [r navg, (r + 1) navg)} |X_s[k]|^2,  k = (j + nfft / 2) mod nfft
+
+    linear power in float32, bin j centred on freqs_hz[j] = (j - nfft / 2) fs / nfft (ascending, as
+    np.fft.fftshift): scipy.signal.spectrogram(x, window=w, nperseg=nfft, noverlap=nfft - hop,
+    detrend=False, return_onesided=False, scaling='spectrum', mode='psd') averaged over groups of
+    navg columns and shifted.  navg = 0: one row of all segments.  Trailing segments that do not
+    fill a row are ignored; nothing is carried between calls.
+
+    nfft: a power of two in [64, 8192].  hop: 1 .. 2^24 (None: nfft), odd or even, larger than
+    nfft for a sparse monitor.  window: a name for scipy.signal.get_window(name, nfft) (periodic),
+    or nfft finite values of any sign whose sum is not zero.  scale = (sum w)^2: out * scale /
+    (fs sum w^2) is the density.  The arguments are checked, and rows / freqs_hz / window / scale
+    answer, before a context exists; the device object is made at the first call that needs it."""
+
+    MIN_NFFT, MAX_NFFT, MAX_HOP = 64, 8192, 1 << 24              # include/sdr.h SDR_SPEC_*
+    SPLIT_SEGS = 8                                               # a row of more segments may be summed in chunks (SDR_SPEC_SPLIT_SEGS)
+
+    def __init__(self, nfft: int, fs: float, hop=None, navg: int = 0, window="hann", iq_dtype=np.float32, ctx=None):
+        self.handle = None
+        nfft, fs, navg = int(nfft), float(fs), int(navg)
+        if not (np.isfinite(fs) and fs > 0):
+            raise ValueError("fs must be positive")
+        if not self.MIN_NFFT <= nfft <= self.MAX_NFFT or nfft & (nfft - 1):
+            raise ValueError(f"nfft={nfft} must be a power of two in [{self.MIN_NFFT}, {self.MAX_NFFT}]")
+        hop = nfft if hop is None else int(hop)
+        if not 1 <= hop <= self.MAX_HOP:
+            raise ValueError(f"hop={hop} outside [1, {self.MAX_HOP}]")
+        if navg < 0:
+            raise ValueError(f"navg={navg} must be 0 (one row) or >= 1")
+        w = design.spectrum_window(window, nfft)
+        dt = np.dtype(iq_dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.uint8)):
+            raise ValueError(f"iq_dtype {dt}: float32 or uint8")
+        self.u8 = dt == np.uint8
+        self.nfft, self.fs, self.hop, self.navg, self.window = nfft, fs, hop, navg, w
+        self.scale = float(np.sum(w)) ** 2
+        self._ctx = ctx
+
+    @property
+    def freqs_hz(self) -> np.ndarray:
+        """The nfft bin centres, ascending: (j - nfft / 2) fs / nfft."""
+        return (np.arange(self.nfft) - self.nfft // 2) * (self.fs / self.nfft)
+
+    def rows(self, n: int):
+        """(nseg, rows) of a call of n samples."""
+        return spectrum_rows(n, self.nfft, self.hop, self.navg)
+
+    def _open(self):
+        if self.handle is None:
+            self.ctx = self._ctx if self._ctx is not None else _lib.get_context()
+            self.lib = self.ctx.lib
+            h = ctypes.c_void_p()
+            check(self.lib.sdr_spec_create(self.ctx.handle, self.nfft, f64p(self.window), self.hop, self.navg,
+                                           SDR_IQ_U8 if self.u8 else SDR_IQ_F32, ctypes.byref(h)), "sdr_spec_create")
+            self.handle = h
+        return self.handle
+
+    def process_dev(self, iq_ptr: int, n: int, out_ptr: int, out_stride=None) -> int:
+        """n complex samples at device pointer iq_ptr -> rows of nfft float32 at out_ptr,
+        out_stride floats apart (None: nfft; the floats between rows are not written); async on
+        the context stream.  Returns the row count."""
+        n = int(n)
+        rows = self.rows(n)[1]
+        out_stride = self.nfft if out_stride is None else int(out_stride)
+        if out_stride < self.nfft:
+            raise ValueError(f"out_stride={out_stride} < nfft={self.nfft}")
+        h = self._open()
+        check(self.lib.sdr_spec_process_dev(h, iq_ptr, n, out_ptr, out_stride), "sdr_spec_process_dev")
+        return rows
+
+    def run(self, iq_host) -> np.ndarray:
+        """n complex samples from the host (interleaved f32 / u8, or complex for an f32 object)
+        -> float32[rows, nfft], synchronous (sdr_spec_run)."""
+        iq = np.asarray(iq_host)
+        if np.iscomplexobj(iq):
+            if self.u8:
+                raise ValueError("a uint8 spectrum takes interleaved uint8 IQ")
+            iq = np.ascontiguousarray(iq, dtype=np.complex64).view(np.float32)
+        iq = np.ascontiguousarray(iq, dtype=np.uint8 if self.u8 else np.float32)
+        if iq.ndim != 1 or iq.size % 2:
+            raise ValueError("expected a 1-D array of interleaved I, Q values")
+        n = iq.size // 2
+        rows = self.rows(n)[1]
+        out = np.empty((rows, self.nfft), dtype=np.float32)
+        h = self._open()
+        check(self.lib.sdr_spec_run(h, iq.ctypes.data, n, out.ctypes.data, self.nfft), "sdr_spec_run")
+        return out
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.sdr_spec_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+FoundChannels = collections.namedtuple("FoundChannels", "index freq_hz snr_db")
+
+
+def find_channels(power_row, fs: float, spacing_hz: float, width_hz=None, min_snr_db: float = 10.0, offset_hz: float = 0.0,
+                  isolated: bool = True) -> FoundChannels:
+    """Which channels of a uniform grid carry a signal, from one Spectrum row (host, numpy).
+
+    power_row: linear power of nbin bins in ascending order, bin i centred on (i - nbin / 2)
+    fs / nbin.  Candidate centres are offset_hz + j spacing_hz for every integer j whose window
+    [f - width / 2, f + width / 2) lies inside [-fs / 2, fs / 2); width_hz defaults to 0.8
+    spacing_hz.  A candidate's power is the sum of the bins whose centres fall in its window; the
+    noise floor per bin is the row's median -- valid while fewer than half of the bins are
+    occupied, so a band more than half full of signals needs a floor from elsewhere -- and the
+    SNR is the candidate's power over (median x bins in its window).  Kept: SNR >= min_snr_db,
+    and with isolated=True a power not below that of either neighbouring candidate (an FM
+    station's skirts reach into the adjacent slots of a 200 kHz grid).
+
+    Returns (index, freq_hz, snr_db), arrays sorted by frequency; index is the signed j.  With
+    spacing_hz == fs / nbins and offset_hz == 0 it is the signed bin numbers
+    FilterBank(nbins, ..., bins=found.index) takes."""
+    p = np.asarray(power_row, dtype=np.float64)
+    fs, spacing, offset = float(fs), float(spacing_hz), float(offset_hz)
+    if p.ndim != 1 or p.size < 2:
+        raise ValueError("power_row: one row of at least two bins")
+    if not (np.isfinite(fs) and fs > 0 and np.isfinite(spacing) and spacing > 0 and np.isfinite(offset)):
+        raise ValueError("fs and spacing_hz must be positive, offset_hz finite")
+    width = 0.8 * spacing if width_hz is None else float(width_hz)
+    if not (np.isfinite(width) and width > 0):
+        raise ValueError("width_hz must be positive")
+    nbin = p.size
+    centres = (np.arange(nbin) - nbin // 2) * (fs / nbin)
+    jlo = int(np.ceil((-fs / 2 + width / 2 - offset) / spacing))
+    jhi = int(np.floor((fs / 2 - width / 2 - offset) / spacing))
+    j = np.arange(jlo, jhi + 1)
+    j = j[(offset + j * spacing - width / 2 >= -fs / 2) & (offset + j * spacing + width / 2 <= fs / 2)]
+    f = offset + j * spacing
+    # bins [lo, hi) of every window: centres ascend, so the window is a slice of the prefix sums
+    lo = np.searchsorted(centres, f - width / 2, side="left")
+    hi = np.searchsorted(centres, f + width / 2, side="left")
+    csum = np.r_[0.0, np.cumsum(p)]
+    power = csum[hi] - csum[lo]
+    floor = float(np.median(p))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        snr = 10.0 * np.log10(power / (floor * (hi - lo)))
+    keep = (hi > lo) & (snr >= float(min_snr_db))
+    if isolated and len(j):
+        left = np.r_[-np.inf, power[:-1]]
+        right = np.r_[power[1:], -np.inf]
+        keep &= (power >= left) & (power >= right)
+    return FoundChannels(j[keep].astype(np.int64), f[keep], snr[keep])

@@ -16,7 +16,7 @@ namespace sdrint {
 // scratch slots owned by a context (grown on demand, never shrunk)
 enum Slot {
   S_IN, S_IN2, S_OUT, S_OUT2, S_OUT3, S_OUT4, S_STATE, S_STATE2, S_MISC, S_THETA, S_PHI, S_WRAP,
-  S_PSD, S_PLLW, S_IIR,
+  S_PSD, S_PLLW, S_IIR, S_SPEC,
   S_NSLOT
 };
 

@@ -157,3 +157,21 @@ def rds_coeffs(taps: int = RF_TAPS):
         anti_img=signal.firwin(taps, (57000 / 2) / ((240000 * 19) / 2), window=("hann")),
         rrc=impulseResponseRootRaisedCosine(RRC_FS, RRC_TAPS),
     )
+
+
+def spectrum_window(window, nfft: int) -> np.ndarray:
+    """The nfft window values of a Spectrum (f64): a name (or tuple) for
+    scipy.signal.get_window(window, nfft) -- the periodic form, as scipy.signal.spectrogram
+    uses -- or an array of nfft finite values of any sign whose sum is not zero."""
+    if isinstance(window, (str, tuple)):
+        w = signal.get_window(window, int(nfft))
+    else:
+        w = np.atleast_1d(np.asarray(window))
+        if w.ndim != 1 or len(w) != nfft or np.iscomplexobj(w):
+            raise ValueError(f"{w.shape} window values: nfft={nfft} real ones")
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if not np.all(np.isfinite(w)):
+        raise ValueError("window values must be finite")
+    if np.sum(w) == 0.0:
+        raise ValueError("the window sums to zero")
+    return w
