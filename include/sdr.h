@@ -448,6 +448,49 @@ int sdr_pfb_position(sdr_pfb* pfb, int64_t* position);
 int sdr_pfb_process_dev(sdr_pfb* pfb, const void* iq, int64_t n, float* out, int64_t out_stride);
 int sdr_pfb_run(sdr_pfb* pfb, const void* iq_host, int64_t n, float* out_host, int64_t out_stride); /* sync */
 
+/* ---- rational resampler for device rows ---------------------------------------------------
+ * nrows rows of f32 samples in device memory, real (elems = SDR_RSMP_REAL) or interleaved
+ * complex (SDR_RSMP_COMPLEX), resampled by up / down through one real filter b of `taps` taps
+ * designed at `up` times the input rate -- the stage between a channelizer whose fs / decim is
+ * not the receiver's rate and the receiver (2.5 MS/s rows x 24/25 -> 2.4 MS/s), or N audio
+ * streams 48 kHz -> 44.1 kHz (147/160).  Per row, sdr_resample's convention, gain included:
+ *   y[m] = up sum_j b[j] xu[m down - j],   xu[i] = x[i / up] if up divides i, else 0
+ * = up lfilter(b, 1, zero-stuff(x, up))[::down], x zero before the stream start and carried
+ * across calls.  Computed in polyphase form, P = ceil(taps / up), b zero-padded to P up,
+ * m down = s up + r with 0 <= r < up:
+ *   y[m] = sum_{q < P} g[r + q up] x[s - q],   g = f32(up b)
+ * an f32 FMA chain over q = 0 .. P - 1 per output and component (the first term a product), so
+ * an output's bits depend only on the taps and on the P samples of its window: any split of a
+ * stream into calls gives the same bits as one call.  A non-finite sample can make non-finite
+ * only the outputs whose window x[s - P + 1 .. s] contains it.
+ * Every call takes n >= 1 samples per row with n up % down == 0 and writes exactly n up / down
+ * per row, so every call starts at phase 0.  The object keeps the last P - 1 input samples of
+ * every row; the input is read in place.  One launch per call for all rows (csrc/rsmp.hip) plus
+ * the history update; a workgroup produces up to SDR_RSMP_TILE outputs of one row as a unit.
+ * Row r starts r stride samples (elems floats each) into its buffer -- sdr_ddc_process_dev's
+ * rows, so complex output rows are what sdr_rx_process_dev reads with iq_stride = out_stride.
+ * in and out are aligned to one sample (4 B real, 8 B complex); the in_stride - n and
+ * out_stride - n up / down samples between rows are not read into any result and not written.
+ * sdr_rsmp_process_dev: async on the context stream.  sdr_rsmp_run: host buffers, synchronous.
+ * SDR_EINVAL (before any device work, history and position unchanged): nrows, elems, taps, up,
+ * down out of range, ceil(taps / up) > SDR_RSMP_MAX_PHASE_TAPS, a non-finite tap, NULL
+ * pointers, n < 1, n up % down != 0, n or n up / down >= 2^31, a stride shorter than its row,
+ * misaligned pointers, out's extent overlapping in's.  No configuration inside the limits is
+ * unsupported, and there is no host fallback. */
+enum { SDR_RSMP_REAL = 1, SDR_RSMP_COMPLEX = 2 };   /* floats per sample */
+#define SDR_RSMP_MAX_FACTOR 1024
+#define SDR_RSMP_MAX_TAPS 4096
+#define SDR_RSMP_MAX_PHASE_TAPS 256
+#define SDR_RSMP_MAX_ROWS 65535
+#define SDR_RSMP_TILE 2048
+typedef struct sdr_rsmp sdr_rsmp;
+int  sdr_rsmp_create(sdr_ctx* ctx, int nrows, int elems, const double* b, int taps, int up, int down, sdr_rsmp** out);
+void sdr_rsmp_destroy(sdr_rsmp* rsmp);
+int  sdr_rsmp_reset(sdr_rsmp* rsmp);                             /* zero history, position 0 */
+int  sdr_rsmp_position(sdr_rsmp* rsmp, int64_t* in_samples);     /* taken per row since the last reset */
+int  sdr_rsmp_process_dev(sdr_rsmp* rsmp, const float* in, int64_t n, int64_t in_stride, float* out, int64_t out_stride); /* async */
+int  sdr_rsmp_run(sdr_rsmp* rsmp, const float* in_host, int64_t n, int64_t in_stride, float* out_host, int64_t out_stride); /* sync */
+
 /* ---- wideband spectrum / waterfall ---------------------------------------------------------
  * Welch periodogram rows of one interleaved-IQ capture in device memory (f32, or u8 as
  * (x - 128) / 128) -- the buffer sdr_ddc_process_dev / sdr_pfb_process_dev read, in place: where

@@ -13,7 +13,8 @@ fused hot-path forms: lfilter_decim, rf_frontend_block, mono_block, resample,
 fm_mono_streams; the audio output stage (FM de-emphasis, int16 PCM): iir1, deemphasis, audio_out;
 device-resident block pipelines: MonoBlockProcessor, StereoBlockProcessor,
 RdsBlockProcessor; the wideband channelizer in front of a Receiver: Channelizer (any
-frequencies) and FilterBank (a uniform grid of bins: the filter's work shared by all channels);
+frequencies) and FilterBank (a uniform grid of bins: the filter's work shared by all channels),
+and RowResampler between them and the Receiver where fs / decim is not its 2.4 MS/s;
 the RDS link layer behind the receiver's RRC rows: RdsLinkLayer (host, one stream) and
 RdsLinkBank (device, every stream of a call), rds_groups; the capture's spectrum / waterfall and the
 station finder in front of them: Spectrum (device), find_channels (host).
@@ -24,7 +25,7 @@ from ._lib import (SDR_IQ_F32, SDR_IQ_U8, SDR_PRE_MIX, SDR_PRE_NONE, SDR_PRE_SQU
                    DeviceBuffer, SdrError, SdrUnavailable, Timer, device_count, device_info, get_context,
                    load_library)
 from .blocks import (Channelizer, FilterBank, MonoBlockProcessor, RdsBlockProcessor, RdsLinkBank, RdsLinkLayer,  # noqa: F401
-                     Receiver, Spectrum, StereoBlockProcessor, find_channels, rds_groups, spectrum_rows)
+                     Receiver, RowResampler, Spectrum, StereoBlockProcessor, find_channels, rds_groups, spectrum_rows)
 from .design import impulseResponseRootRaisedCosine, my_filterImpulseResponse  # noqa: F401
 from .dsp import (DFT, MonoState, estimatePSD, fm_mono_range, fm_mono_streams, split_halo, fmDemodArctan, fmPll, lfilter, lfilter_decim,  # noqa: F401
                   audio_out, deemphasis, iir1, mono_block, my_convoloution, resample, rf_frontend_block)

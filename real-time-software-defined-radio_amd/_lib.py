@@ -132,6 +132,12 @@ SIGNATURES = {
     "sdr_pfb_position": (_i32, [_vp, _c.POINTER(_i64)]),
     "sdr_pfb_process_dev": (_i32, [_vp, _vp, _i64, _vp, _i64]),
     "sdr_pfb_run": (_i32, [_vp, _vp, _i64, _vp, _i64]),
+    "sdr_rsmp_create": (_i32, [_vp, _i32, _i32, _dp, _i32, _i32, _i32, _c.POINTER(_vp)]),
+    "sdr_rsmp_destroy": (None, [_vp]),
+    "sdr_rsmp_reset": (_i32, [_vp]),
+    "sdr_rsmp_position": (_i32, [_vp, _c.POINTER(_i64)]),
+    "sdr_rsmp_process_dev": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64]),
+    "sdr_rsmp_run": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64]),
     "sdr_spec_create": (_i32, [_vp, _i32, _dp, _i64, _i64, _i32, _c.POINTER(_vp)]),
     "sdr_spec_destroy": (None, [_vp]),
     "sdr_spec_rows": (_i32, [_vp, _i64, _c.POINTER(_i64), _c.POINTER(_i64)]),

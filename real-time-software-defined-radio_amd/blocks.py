@@ -742,6 +742,109 @@ class FilterBank:
             pass
 
 
+class RowResampler:
+    """A rational up / down resampler for `nrows` rows of device memory (sdr_rsmp,
+    csrc/rsmp.hip), complex or real f32: the stage between a channelizer or filter bank whose
+    fs / decim is not the receiver's 2.4 MS/s and the Receiver (2.5 MS/s rows x 24/25), or N
+    audio streams 48 kHz -> 44.1 kHz (147/160).  Per row and component
+    up x lfilter(taps, 1, zero-stuff(x, up))[::down] (= up x scipy.signal.upfirdn(taps, x, up,
+    down) cut to length), as a polyphase f32 FMA chain per output.
+
+    taps: an array of real taps designed at `up` times the input rate, a tap count, or None
+    (design.resample_coeffs(up, down): scipy.signal.resample_poly's default filter; with it and
+    down >= up, output m + 10 is resample_poly(x, up, down)[m]).  At most MAX_TAPS taps and
+    MAX_PHASE_TAPS per phase (ceil(taps / up)).  Every call takes n samples per row with
+    n up % down == 0 and gives n up / down; the last ceil(taps / up) - 1 samples of every row
+    and the position are carried from call to call, and any split of a stream into calls gives
+    the same bits as one call.
+
+    process(x) takes a host (nrows, n) complex64 (float32 for a real object) array and returns
+    (nrows, n up / down); process_dev works on device memory in place: row r starts r stride
+    samples into its buffer -- a complex object's output rows are what Receiver.process_dev
+    reads with iq_stride = out_stride."""
+
+    MAX_FACTOR, MAX_TAPS, MAX_PHASE_TAPS, MAX_ROWS = 1024, 4096, 256, 65535      # include/sdr.h SDR_RSMP_MAX_*
+    TILE = 2048                                                                  # outputs a workgroup produces as a unit (SDR_RSMP_TILE)
+
+    def __init__(self, nrows: int, up: int, down: int, taps=None, complex: bool = True, ctx=None):
+        self.handle = None
+        nrows, up, down = int(nrows), int(up), int(down)
+        if not 1 <= nrows <= self.MAX_ROWS:
+            raise ValueError(f"nrows={nrows} outside [1, {self.MAX_ROWS}]")
+        if not 1 <= up <= self.MAX_FACTOR:
+            raise ValueError(f"up={up} outside [1, {self.MAX_FACTOR}]")
+        if not 1 <= down <= self.MAX_FACTOR:
+            raise ValueError(f"down={down} outside [1, {self.MAX_FACTOR}]")
+        if taps is None or np.ndim(taps) == 0:
+            if taps is not None and not 1 <= int(taps) <= self.MAX_TAPS:
+                raise ValueError(f"taps={taps} outside [1, {self.MAX_TAPS}]")
+            taps = design.resample_coeffs(up, down, taps)
+        b = np.ascontiguousarray(np.atleast_1d(np.asarray(taps)), dtype=np.float64)
+        if b.ndim != 1 or not 1 <= len(b) <= self.MAX_TAPS:
+            raise ValueError(f"{b.shape} taps: 1..{self.MAX_TAPS} real taps")
+        if -(-len(b) // up) > self.MAX_PHASE_TAPS:
+            raise ValueError(f"{len(b)} taps at up={up}: more than {self.MAX_PHASE_TAPS} taps per phase")
+        if not np.all(np.isfinite(b)):
+            raise ValueError("taps must be finite")
+        self.nrows, self.up, self.down, self.taps, self.complex = nrows, up, down, b, bool(complex)
+        self.elems = 2 if self.complex else 1
+        self.step = down // int(np.gcd(up, down))       # a call's n is a multiple of this
+        self.ctx = ctx if ctx is not None else _lib.get_context()
+        self.lib = self.ctx.lib
+        h = ctypes.c_void_p()
+        check(self.lib.sdr_rsmp_create(self.ctx.handle, nrows, self.elems, f64p(b), len(b), up, down, ctypes.byref(h)),
+              "sdr_rsmp_create")
+        self.handle = h
+
+    @property
+    def position(self) -> int:
+        """Input samples taken per row since the last reset."""
+        p = ctypes.c_int64()
+        check(self.lib.sdr_rsmp_position(self.handle, ctypes.byref(p)), "sdr_rsmp_position")
+        return p.value
+
+    def reset(self):
+        """Zero the history of every row; the position back to 0."""
+        check(self.lib.sdr_rsmp_reset(self.handle), "sdr_rsmp_reset")
+
+    def out_len(self, n: int) -> int:
+        """Outputs per row of a call of n samples per row (n up / down)."""
+        n = int(n)
+        if n < 1 or n % self.step:
+            raise ValueError(f"n={n} must be >= 1 and a multiple of down/gcd(up, down)={self.step}")
+        return n * self.up // self.down
+
+    def process(self, x) -> np.ndarray:
+        """(nrows, n) samples from the host -> (nrows, n up / down), synchronous (sdr_rsmp_run)."""
+        x = np.ascontiguousarray(x, dtype=np.complex64 if self.complex else np.float32)
+        if x.ndim != 2 or x.shape[0] != self.nrows:
+            raise ValueError(f"expected an array of shape ({self.nrows}, n)")
+        n = x.shape[1]
+        mo = self.out_len(n)
+        out = np.empty((self.nrows, mo), dtype=x.dtype)
+        check(self.lib.sdr_rsmp_run(self.handle, x.ctypes.data, n, n, out.ctypes.data, mo), "sdr_rsmp_run")
+        return out
+
+    def process_dev(self, in_ptr: int, n: int, in_stride: int, out_ptr: int, out_stride: int):
+        """n samples per row at device pointer in_ptr, rows in_stride samples apart -> n up / down
+        samples per row at out_ptr, rows out_stride samples apart; async on the context stream."""
+        n, in_stride, out_stride = int(n), int(in_stride), int(out_stride)
+        mo = self.out_len(n)
+        if in_stride < n or out_stride < mo:
+            raise ValueError(f"in_stride={in_stride} < n={n} or out_stride={out_stride} < n up/down={mo}")
+        check(self.lib.sdr_rsmp_process_dev(self.handle, in_ptr, n, in_stride, out_ptr, out_stride), "sdr_rsmp_process_dev")
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.sdr_rsmp_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 def spectrum_rows(n: int, nfft: int, hop: int, navg: int):
     """(nseg, rows) of a Spectrum call of n samples: nseg = (n - nfft) // hop + 1 segments,

@@ -81,6 +81,21 @@ def pfb_coeffs(nbins: int, taps_per_bin: int = 8) -> np.ndarray:
     return signal.firwin(nbins * taps_per_bin, 1.0 / nbins)
 
 
+def resample_coeffs(up: int, down: int, taps=None) -> np.ndarray:
+    """The row resampler's low-pass (RowResampler, sdr_rsmp), designed at `up` times the input
+    rate: signal.firwin(T, 1 / max(up, down), window=('kaiser', 5.0)) with T = taps or
+    min(20 max(up, down) + 1, 4096) -- scipy.signal.resample_poly's default filter (unit DC gain;
+    the resampler applies the gain `up`), cut to the library's longest filter."""
+    up, down = int(up), int(down)
+    if up < 1 or down < 1:
+        raise ValueError("up and down must be >= 1")
+    big = max(up, down)
+    taps = int(taps) if taps else min(20 * big + 1, 4096)
+    if taps < 1:
+        raise ValueError("taps must be >= 1")
+    return signal.firwin(taps, 1.0 / big, window=("kaiser", 5.0))
+
+
 def ddc_phase_inc(nu: float) -> int:
     """The channelizer's phase increment for a frequency of nu cycles per sample
     (|nu| <= 0.5): rint(nu 2^32) mod 2^32, as a Python int in [0, 2^32)."""
