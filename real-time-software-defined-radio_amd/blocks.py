@@ -38,7 +38,115 @@ def _addr(a):
     return a.ctypes.data
 
 
-class Receiver:
+class _Handle:
+    """A libsdr object: `lib`, its `handle` (None until created, and again once closed, so that
+    __del__ is safe after a failed constructor) and the C prefix of its functions."""
+
+    _prefix = None
+    handle = None
+
+    def _do(self, op, *args):
+        name = f"{self._prefix}_{op}"
+        check(getattr(self.lib, name)(self.handle, *args), name)
+
+    def close(self):
+        if self.handle:
+            getattr(self.lib, f"{self._prefix}_destroy")(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _Stream(_Handle):
+    """A block that carries a history and a stream position from call to call."""
+
+    @property
+    def position(self) -> int:
+        """Input samples taken since the last reset (plus its position, where it takes one)."""
+        p = ctypes.c_int64()
+        self._do("position", ctypes.byref(p))
+        return p.value
+
+    def reset(self):
+        """Zero the history of every row; the position back to 0."""
+        self._do("reset")
+
+
+class _DecimBlock(_Stream):
+    """One interleaved-IQ capture to `nch` rows at fs / decim (Channelizer, FilterBank): the
+    call rules and the two entry points."""
+
+    _noun = None
+
+    def reset(self, position: int = 0):
+        """Zero the filter history and set the stream position (>= 0, a multiple of decim)."""
+        self._do("reset", int(position))
+
+    def _check_n(self, n, out_stride=None):
+        if n < 1 or n % self.decim:
+            raise ValueError(f"n={n} must be >= 1 and a multiple of decim={self.decim}")
+        if out_stride is not None and out_stride < n // self.decim:
+            raise ValueError(f"out_stride={out_stride} < n/decim={n // self.decim}")
+
+    def process(self, iq) -> np.ndarray:
+        """n complex samples from the host (interleaved f32 / u8, or complex for an f32
+        object) -> (nch, n / decim) complex64, synchronous (sdr_ddc_run / sdr_pfb_run)."""
+        iq = _interleaved_iq(iq, self.u8, self._noun)
+        n = iq.size // 2
+        self._check_n(n)
+        out = np.empty((self.nch, n // self.decim), dtype=np.complex64)
+        self._do("run", iq.ctypes.data, n, out.ctypes.data, n // self.decim)
+        return out
+
+    def process_dev(self, iq_ptr: int, n: int, out_ptr: int, out_stride: int):
+        """n complex samples at device pointer iq_ptr -> rows of n / decim complex f32 at
+        out_ptr, out_stride complex samples apart; async on the context stream."""
+        n, out_stride = int(n), int(out_stride)
+        self._check_n(n, out_stride)
+        self._do("process_dev", iq_ptr, n, out_ptr, out_stride)
+
+
+def _interleaved_iq(iq, u8, noun):
+    """A host capture as a 1-D array of interleaved I, Q values of the object's type."""
+    iq = np.asarray(iq)
+    if np.iscomplexobj(iq):
+        if u8:
+            raise ValueError(f"a uint8 {noun} takes interleaved uint8 IQ")
+        iq = np.ascontiguousarray(iq, dtype=np.complex64).view(np.float32)
+    iq = np.ascontiguousarray(iq, dtype=np.uint8 if u8 else np.float32)
+    if iq.ndim != 1 or iq.size % 2:
+        raise ValueError("expected a 1-D array of interleaved I, Q values")
+    return iq
+
+
+def _real_taps(taps, max_taps, designed, count_checked=True):
+    """A `taps` argument -- an array of real taps, a tap count or None -- as 1 .. max_taps finite
+    float64 taps; designed(count or None) makes the last two."""
+    if taps is None or np.ndim(taps) == 0:
+        if count_checked and taps is not None and not 1 <= int(taps) <= max_taps:
+            raise ValueError(f"taps={taps} outside [1, {max_taps}]")
+        taps = designed(taps)
+    b = np.ascontiguousarray(np.atleast_1d(np.asarray(taps)), dtype=np.float64)
+    if b.ndim != 1 or not 1 <= len(b) <= max_taps:
+        raise ValueError(f"{b.shape} taps: 1..{max_taps} real taps")
+    if not np.all(np.isfinite(b)):
+        raise ValueError("taps must be finite")
+    return b
+
+
+def _is_u8(iq_dtype):
+    """An `iq_dtype` argument: float32 (False) or uint8 (True)."""
+    dt = np.dtype(iq_dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.uint8)):
+        raise ValueError(f"iq_dtype {dt}: float32 or uint8")
+    return dt == np.uint8
+
+
+class Receiver(_Handle):
     """`nstreams` independent FM streams through the block receiver (sdr_rx).
 
     Each call to process() takes one block of every stream: an (nstreams, 2*block) array of
@@ -54,6 +162,8 @@ class Receiver:
     audio rows through design.deemphasis_coeffs(deemphasis, 240 kHz / audio_decim) on the device
     (sdr_rx_set_deemph), state carried from block to block -- and pcm(), the block's interleaved
     int16 samples; process()'s default outputs include the de-emphasised rows."""
+
+    _prefix = "sdr_rx"
 
     def __init__(self, nstreams: int, block_complex: int, *, mono: bool = True, stereo: bool = False,
                  rds: bool = False, iq_dtype=np.uint8, rf_coeff=None, audio_coeff=None, stereo_taps: int = 151,
@@ -257,17 +367,6 @@ class Receiver:
         check(self.lib.sdr_rx_stage_ms(self.handle, ms.ctypes.data_as(_lib._fp)), "sdr_rx_stage_ms")
         return dict(zip(_lib.RX_STAGES, (float(v) for v in ms)))
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.sdr_rx_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class MonoBlockProcessor:
     """FE (RF LPF + decimate + atan2 demod) and mono audio LPF + decimate per block.
@@ -343,7 +442,7 @@ class RdsBlockProcessor(MonoBlockProcessor):
         return self._run(iq_block, names)
 
 
-class RdsLinkLayer:
+class RdsLinkLayer(_Handle):
     """RDS link layer of model/fmRDSblock.py:207-346 on the host (libsdr C++, no GPU):
     clock and data recovery, Manchester and differential decoding, syndrome frame sync.
 
@@ -354,6 +453,7 @@ class RdsLinkLayer:
 
     TYPES = "ABCD"
     RESYNC = 4
+    _prefix = "sdr_rds_link"
 
     def __init__(self, resync_after: int = 0):
         """resync_after > 0: the C++ frame_thread's rule (src/fm_radio.cpp:697-704; it uses
@@ -388,19 +488,8 @@ class RdsLinkLayer:
         return dict(events=events, symbols=sym[:ns.value].copy(), bits=bits[:nb.value].copy(),
                     diff=diff[:nd.value].copy())
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.sdr_rds_link_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class RdsLinkBank:
+class RdsLinkBank(_Handle):
     """RdsLinkLayer for `nstreams` streams at once, on the GPU (sdr_rds_links, csrc/rds.hip): the
     in-phase RRC rows are read where the receiver left them, every stream's link state stays in
     device memory, and what comes back is the events -- per stream a list of
@@ -418,9 +507,9 @@ class RdsLinkBank:
     RESYNC = 4
     MIN_N = _lib.SDR_RDS_LINKS_MIN_N
     FAULT, OVERFLOW = _lib.SDR_RDS_LINKS_FAULT, _lib.SDR_RDS_LINKS_OVERFLOW
+    _prefix = "sdr_rds_links"
 
     def __init__(self, nstreams: int, max_n: int, *, max_events=None, resync_after: int = 0, ctx=None):
-        self.handle = None
         self.S, self.max_n = int(nstreams), int(max_n)
         # a call scans at most (max_n / 24) / 2 + 2 windows, and a window gives at most two events
         self.max_events = int(max_events) if max_events is not None else min(2 * (self.max_n // 48 + 4), 4096)
@@ -476,17 +565,6 @@ class RdsLinkBank:
         """Every stream back to block 0."""
         check(self.lib.sdr_rds_links_reset(self.handle), "sdr_rds_links_reset")
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.sdr_rds_links_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def rds_groups(events):
     """One stream's events -> the groups in them: an accepted A at position p with accepted B, C,
@@ -500,7 +578,7 @@ def rds_groups(events):
     return groups
 
 
-class Channelizer:
+class Channelizer(_DecimBlock):
     """One wideband IQ capture to `len(freqs_hz)` receiver streams on the GPU (sdr_ddc,
     csrc/ddc.hip): per channel "mix down by freqs_hz[c], lfilter(taps, 1, .), [::decim]", all
     channels in one matrix-core launch.  The reference has no channelizer; this is the stage in
@@ -521,9 +599,9 @@ class Channelizer:
 
     MAX_CH, MAX_TAPS, MAX_DECIM = 64, 256, 64      # include/sdr.h SDR_DDC_MAX_*
     WINDOW = 64                                    # outputs per wave window (SDR_DDC_WINDOW)
+    _prefix, _noun = "sdr_ddc", "channelizer"
 
     def __init__(self, freqs_hz, fs: float, decim: int, taps=None, iq_dtype=np.float32, ctx=None):
-        self.handle = None
         fs, decim = float(fs), int(decim)
         if not (np.isfinite(fs) and fs > 0):
             raise ValueError("fs must be positive")
@@ -534,17 +612,8 @@ class Channelizer:
             raise ValueError(f"{f.shape} channel frequencies: 1..{self.MAX_CH} channels")
         if not np.all(np.isfinite(f)) or np.any(np.abs(f / fs) > 0.5):
             raise ValueError("channel frequencies must be finite and within [-fs/2, fs/2]")
-        if taps is None or np.ndim(taps) == 0:
-            taps = design.channel_coeffs(decim, taps)
-        b = np.ascontiguousarray(np.atleast_1d(np.asarray(taps)), dtype=np.float64)
-        if b.ndim != 1 or not 1 <= len(b) <= self.MAX_TAPS:
-            raise ValueError(f"{b.shape} taps: 1..{self.MAX_TAPS} real taps")
-        if not np.all(np.isfinite(b)):
-            raise ValueError("taps must be finite")
-        dt = np.dtype(iq_dtype)
-        if dt not in (np.dtype(np.float32), np.dtype(np.uint8)):
-            raise ValueError(f"iq_dtype {dt}: float32 or uint8")
-        self.u8 = dt == np.uint8
+        b = _real_taps(taps, self.MAX_TAPS, lambda t: design.channel_coeffs(decim, t), count_checked=False)
+        self.u8 = _is_u8(iq_dtype)
         self.fs, self.decim, self.taps, self.nch = fs, decim, b, len(f)
         self.inc = [design.ddc_phase_inc(v / fs) for v in f]
         self.ctx = ctx if ctx is not None else _lib.get_context()
@@ -562,60 +631,8 @@ class Channelizer:
         check(self.lib.sdr_ddc_freq(self.handle, f64p(nu)), "sdr_ddc_freq")
         return nu * self.fs
 
-    @property
-    def position(self) -> int:
-        """Input samples taken since the last reset (plus its position)."""
-        p = ctypes.c_int64()
-        check(self.lib.sdr_ddc_position(self.handle, ctypes.byref(p)), "sdr_ddc_position")
-        return p.value
 
-    def reset(self, position: int = 0):
-        """Zero the filter history and set the stream position (>= 0, a multiple of decim)."""
-        check(self.lib.sdr_ddc_reset(self.handle, int(position)), "sdr_ddc_reset")
-
-    def _check_n(self, n, out_stride=None):
-        if n < 1 or n % self.decim:
-            raise ValueError(f"n={n} must be >= 1 and a multiple of decim={self.decim}")
-        if out_stride is not None and out_stride < n // self.decim:
-            raise ValueError(f"out_stride={out_stride} < n/decim={n // self.decim}")
-
-    def process(self, iq) -> np.ndarray:
-        """n complex samples from the host (interleaved f32 / u8, or complex for an f32
-        object) -> (nch, n / decim) complex64, synchronous (sdr_ddc_run)."""
-        iq = np.asarray(iq)
-        if np.iscomplexobj(iq):
-            if self.u8:
-                raise ValueError("a uint8 channelizer takes interleaved uint8 IQ")
-            iq = np.ascontiguousarray(iq, dtype=np.complex64).view(np.float32)
-        iq = np.ascontiguousarray(iq, dtype=np.uint8 if self.u8 else np.float32)
-        if iq.ndim != 1 or iq.size % 2:
-            raise ValueError("expected a 1-D array of interleaved I, Q values")
-        n = iq.size // 2
-        self._check_n(n)
-        out = np.empty((self.nch, n // self.decim), dtype=np.complex64)
-        check(self.lib.sdr_ddc_run(self.handle, iq.ctypes.data, n, out.ctypes.data, n // self.decim), "sdr_ddc_run")
-        return out
-
-    def process_dev(self, iq_ptr: int, n: int, out_ptr: int, out_stride: int):
-        """n complex samples at device pointer iq_ptr -> rows of n / decim complex f32 at
-        out_ptr, out_stride complex samples apart; async on the context stream."""
-        n, out_stride = int(n), int(out_stride)
-        self._check_n(n, out_stride)
-        check(self.lib.sdr_ddc_process_dev(self.handle, iq_ptr, n, out_ptr, out_stride), "sdr_ddc_process_dev")
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.sdr_ddc_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class FilterBank:
+class FilterBank(_DecimBlock):
     """A polyphase filter bank on the GPU (sdr_pfb, csrc/pfb.hip): one wideband IQ capture to
     the selected bins of a uniform grid of `nbins` across the capture, bin k centred on
     k / nbins x fs (bins >= nbins / 2 are the negative frequencies), each at fs / decim.  Per
@@ -638,9 +655,9 @@ class FilterBank:
 
     MAX_BINS, MAX_CH, MAX_TAPS, MAX_DECIM = 256, 256, 4096, 64      # include/sdr.h SDR_PFB_MAX_*
     WINDOW = 64                                                     # output times per window (SDR_PFB_WINDOW)
+    _prefix, _noun = "sdr_pfb", "filter bank"
 
     def __init__(self, nbins: int, fs: float, decim: int, bins=None, taps=None, iq_dtype=np.float32, ctx=None):
-        self.handle = None
         nbins, fs, decim = int(nbins), float(fs), int(decim)
         if not (np.isfinite(fs) and fs > 0):
             raise ValueError("fs must be positive")
@@ -656,22 +673,12 @@ class FilterBank:
         k = k.astype(np.int64)
         if np.any(2 * k < -nbins) or np.any(k >= nbins):
             raise ValueError(f"bins must lie in [-nbins/2, nbins) with nbins={nbins}")
-        if taps is None or np.ndim(taps) == 0:
-            if taps is not None and not 1 <= int(taps) <= self.MAX_TAPS:
-                raise ValueError(f"taps={taps} outside [1, {self.MAX_TAPS}]")
-            if taps is None:
-                taps = design.pfb_coeffs(nbins)
-            else:                                   # a tap count: the same prototype at that length
-                taps = design.signal.firwin(int(taps), 1.0 / nbins) if nbins > 1 else np.eye(1, int(taps))[0]
-        b = np.ascontiguousarray(np.atleast_1d(np.asarray(taps)), dtype=np.float64)
-        if b.ndim != 1 or not 1 <= len(b) <= self.MAX_TAPS:
-            raise ValueError(f"{b.shape} taps: 1..{self.MAX_TAPS} real taps")
-        if not np.all(np.isfinite(b)):
-            raise ValueError("taps must be finite")
-        dt = np.dtype(iq_dtype)
-        if dt not in (np.dtype(np.float32), np.dtype(np.uint8)):
-            raise ValueError(f"iq_dtype {dt}: float32 or uint8")
-        self.u8 = dt == np.uint8
+        def designed(count):                        # a tap count: the same prototype at that length
+            if count is None:
+                return design.pfb_coeffs(nbins)
+            return design.signal.firwin(int(count), 1.0 / nbins) if nbins > 1 else np.eye(1, int(count))[0]
+        b = _real_taps(taps, self.MAX_TAPS, designed)
+        self.u8 = _is_u8(iq_dtype)
         self.nbins, self.fs, self.decim, self.taps = nbins, fs, decim, b
         self.bins = np.ascontiguousarray(k % nbins, dtype=np.int32)
         self.nch = len(self.bins)
@@ -689,60 +696,8 @@ class FilterBank:
         k = self.bins.astype(np.int64)
         return np.where(2 * k >= self.nbins, k - self.nbins, k) / self.nbins * self.fs
 
-    @property
-    def position(self) -> int:
-        """Input samples taken since the last reset (plus its position)."""
-        p = ctypes.c_int64()
-        check(self.lib.sdr_pfb_position(self.handle, ctypes.byref(p)), "sdr_pfb_position")
-        return p.value
 
-    def reset(self, position: int = 0):
-        """Zero the filter history and set the stream position (>= 0, a multiple of decim)."""
-        check(self.lib.sdr_pfb_reset(self.handle, int(position)), "sdr_pfb_reset")
-
-    def _check_n(self, n, out_stride=None):
-        if n < 1 or n % self.decim:
-            raise ValueError(f"n={n} must be >= 1 and a multiple of decim={self.decim}")
-        if out_stride is not None and out_stride < n // self.decim:
-            raise ValueError(f"out_stride={out_stride} < n/decim={n // self.decim}")
-
-    def process(self, iq) -> np.ndarray:
-        """n complex samples from the host (interleaved f32 / u8, or complex for an f32
-        object) -> (nch, n / decim) complex64, synchronous (sdr_pfb_run)."""
-        iq = np.asarray(iq)
-        if np.iscomplexobj(iq):
-            if self.u8:
-                raise ValueError("a uint8 filter bank takes interleaved uint8 IQ")
-            iq = np.ascontiguousarray(iq, dtype=np.complex64).view(np.float32)
-        iq = np.ascontiguousarray(iq, dtype=np.uint8 if self.u8 else np.float32)
-        if iq.ndim != 1 or iq.size % 2:
-            raise ValueError("expected a 1-D array of interleaved I, Q values")
-        n = iq.size // 2
-        self._check_n(n)
-        out = np.empty((self.nch, n // self.decim), dtype=np.complex64)
-        check(self.lib.sdr_pfb_run(self.handle, iq.ctypes.data, n, out.ctypes.data, n // self.decim), "sdr_pfb_run")
-        return out
-
-    def process_dev(self, iq_ptr: int, n: int, out_ptr: int, out_stride: int):
-        """n complex samples at device pointer iq_ptr -> rows of n / decim complex f32 at
-        out_ptr, out_stride complex samples apart; async on the context stream."""
-        n, out_stride = int(n), int(out_stride)
-        self._check_n(n, out_stride)
-        check(self.lib.sdr_pfb_process_dev(self.handle, iq_ptr, n, out_ptr, out_stride), "sdr_pfb_process_dev")
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.sdr_pfb_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class RowResampler:
+class RowResampler(_Stream):
     """A rational up / down resampler for `nrows` rows of device memory (sdr_rsmp,
     csrc/rsmp.hip), complex or real f32: the stage between a channelizer or filter bank whose
     fs / decim is not the receiver's 2.4 MS/s and the Receiver (2.5 MS/s rows x 24/25), or N
@@ -765,9 +720,9 @@ class RowResampler:
 
     MAX_FACTOR, MAX_TAPS, MAX_PHASE_TAPS, MAX_ROWS = 1024, 4096, 256, 65535      # include/sdr.h SDR_RSMP_MAX_*
     TILE = 2048                                                                  # outputs a workgroup produces as a unit (SDR_RSMP_TILE)
+    _prefix = "sdr_rsmp"
 
     def __init__(self, nrows: int, up: int, down: int, taps=None, complex: bool = True, ctx=None):
-        self.handle = None
         nrows, up, down = int(nrows), int(up), int(down)
         if not 1 <= nrows <= self.MAX_ROWS:
             raise ValueError(f"nrows={nrows} outside [1, {self.MAX_ROWS}]")
@@ -775,17 +730,9 @@ class RowResampler:
             raise ValueError(f"up={up} outside [1, {self.MAX_FACTOR}]")
         if not 1 <= down <= self.MAX_FACTOR:
             raise ValueError(f"down={down} outside [1, {self.MAX_FACTOR}]")
-        if taps is None or np.ndim(taps) == 0:
-            if taps is not None and not 1 <= int(taps) <= self.MAX_TAPS:
-                raise ValueError(f"taps={taps} outside [1, {self.MAX_TAPS}]")
-            taps = design.resample_coeffs(up, down, taps)
-        b = np.ascontiguousarray(np.atleast_1d(np.asarray(taps)), dtype=np.float64)
-        if b.ndim != 1 or not 1 <= len(b) <= self.MAX_TAPS:
-            raise ValueError(f"{b.shape} taps: 1..{self.MAX_TAPS} real taps")
+        b = _real_taps(taps, self.MAX_TAPS, lambda t: design.resample_coeffs(up, down, t))
         if -(-len(b) // up) > self.MAX_PHASE_TAPS:
             raise ValueError(f"{len(b)} taps at up={up}: more than {self.MAX_PHASE_TAPS} taps per phase")
-        if not np.all(np.isfinite(b)):
-            raise ValueError("taps must be finite")
         self.nrows, self.up, self.down, self.taps, self.complex = nrows, up, down, b, bool(complex)
         self.elems = 2 if self.complex else 1
         self.step = down // int(np.gcd(up, down))       # a call's n is a multiple of this
@@ -795,17 +742,6 @@ class RowResampler:
         check(self.lib.sdr_rsmp_create(self.ctx.handle, nrows, self.elems, f64p(b), len(b), up, down, ctypes.byref(h)),
               "sdr_rsmp_create")
         self.handle = h
-
-    @property
-    def position(self) -> int:
-        """Input samples taken per row since the last reset."""
-        p = ctypes.c_int64()
-        check(self.lib.sdr_rsmp_position(self.handle, ctypes.byref(p)), "sdr_rsmp_position")
-        return p.value
-
-    def reset(self):
-        """Zero the history of every row; the position back to 0."""
-        check(self.lib.sdr_rsmp_reset(self.handle), "sdr_rsmp_reset")
 
     def out_len(self, n: int) -> int:
         """Outputs per row of a call of n samples per row (n up / down)."""
@@ -834,17 +770,6 @@ class RowResampler:
             raise ValueError(f"in_stride={in_stride} < n={n} or out_stride={out_stride} < n up/down={mo}")
         check(self.lib.sdr_rsmp_process_dev(self.handle, in_ptr, n, in_stride, out_ptr, out_stride), "sdr_rsmp_process_dev")
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.sdr_rsmp_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def spectrum_rows(n: int, nfft: int, hop: int, navg: int):
     """(nseg, rows) of a Spectrum call of n samples: nseg = (n - nfft) // hop + 1 segments,
@@ -859,7 +784,7 @@ def spectrum_rows(n: int, nfft: int, hop: int, navg: int):
     return nseg, rows
 
 
-class Spectrum:
+class Spectrum(_Handle):
     """The spectrum / waterfall of a wideband IQ capture on the GPU (sdr_spec, csrc/spectrum.hip):
     Welch periodogram rows of the buffer Channelizer / FilterBank read, in place -- which of the
     band's channels carry a station?  With segment s starting at sample s hop and window w,
@@ -881,9 +806,9 @@ class Spectrum:
 
     MIN_NFFT, MAX_NFFT, MAX_HOP = 64, 8192, 1 << 24              # include/sdr.h SDR_SPEC_*
     SPLIT_SEGS = 8                                               # a row of more segments may be summed in chunks (SDR_SPEC_SPLIT_SEGS)
+    _prefix = "sdr_spec"
 
     def __init__(self, nfft: int, fs: float, hop=None, navg: int = 0, window="hann", iq_dtype=np.float32, ctx=None):
-        self.handle = None
         nfft, fs, navg = int(nfft), float(fs), int(navg)
         if not (np.isfinite(fs) and fs > 0):
             raise ValueError("fs must be positive")
@@ -895,10 +820,7 @@ class Spectrum:
         if navg < 0:
             raise ValueError(f"navg={navg} must be 0 (one row) or >= 1")
         w = design.spectrum_window(window, nfft)
-        dt = np.dtype(iq_dtype)
-        if dt not in (np.dtype(np.float32), np.dtype(np.uint8)):
-            raise ValueError(f"iq_dtype {dt}: float32 or uint8")
-        self.u8 = dt == np.uint8
+        self.u8 = _is_u8(iq_dtype)
         self.nfft, self.fs, self.hop, self.navg, self.window = nfft, fs, hop, navg, w
         self.scale = float(np.sum(w)) ** 2
         self._ctx = ctx
@@ -938,31 +860,13 @@ class Spectrum:
     def run(self, iq_host) -> np.ndarray:
         """n complex samples from the host (interleaved f32 / u8, or complex for an f32 object)
         -> float32[rows, nfft], synchronous (sdr_spec_run)."""
-        iq = np.asarray(iq_host)
-        if np.iscomplexobj(iq):
-            if self.u8:
-                raise ValueError("a uint8 spectrum takes interleaved uint8 IQ")
-            iq = np.ascontiguousarray(iq, dtype=np.complex64).view(np.float32)
-        iq = np.ascontiguousarray(iq, dtype=np.uint8 if self.u8 else np.float32)
-        if iq.ndim != 1 or iq.size % 2:
-            raise ValueError("expected a 1-D array of interleaved I, Q values")
+        iq = _interleaved_iq(iq_host, self.u8, "spectrum")
         n = iq.size // 2
         rows = self.rows(n)[1]
         out = np.empty((rows, self.nfft), dtype=np.float32)
         h = self._open()
         check(self.lib.sdr_spec_run(h, iq.ctypes.data, n, out.ctypes.data, self.nfft), "sdr_spec_run")
         return out
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.sdr_spec_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 FoundChannels = collections.namedtuple("FoundChannels", "index freq_hz snr_db")

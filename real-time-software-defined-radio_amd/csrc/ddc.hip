@@ -25,9 +25,9 @@
 // neighbouring windows' 2 (T - 1) + pad floats of overlap come from L2.  The next window's loads
 // are issued before this window's MFMAs.  Interior windows load 16 B (f32) / 4 B (u8) per lane
 // from a descriptor that covers exactly the window; the windows that touch the call's first
-// 2 (T - 1) floats or its end load complex samples one by one from two descriptors -- the
-// object's history (the T - 1 samples before the call) and the caller's buffer, each reading 0
-// outside its range, OR-ed -- so the input is read in place and no access leaves either buffer.
+// 2 (T - 1) floats or its end load complex samples one by one across the seam between the
+// object's history (the T - 1 samples before the call) and the caller's buffer (sdr_stream.h), so
+// the input is read in place and no access leaves either buffer.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,6 +39,7 @@
 
 #include "sdr_ctx.h"
 #include "sdr_mma.h"
+#include "sdr_stream.h"
 
 using namespace sdrint;
 
@@ -53,7 +54,6 @@ static_assert(16 * DDC_CB == SDR_DDC_WINDOW, "the window the header names");
 static_assert(DDC_WAVES * DDC_LP_MAX * 2 * sizeof(_Float16) + DDC_INC_HALFS * 2 <= 64 * 1024, "hi and lo planes of every wave in 64 KB of LDS");
 
 typedef _Float16 h8a4 __attribute__((ext_vector_type(8), aligned(4)));   // a fragment at a 4-B aligned LDS address
-typedef uint32_t u2v __attribute__((ext_vector_type(2)));
 
 struct DdcArgs {
   const void* iq;          // the call's n complex samples (f32 pairs or u8 pairs)
@@ -69,31 +69,6 @@ struct DdcArgs {
   int nch, T, D, KS, NT, nq, lp;
   int a_lds;               // bytes of A fragments the workgroup keeps in LDS (0: read from afrag each K step)
 };
-
-// A32: [16 NT][32 KS] f32 rows -> fragments (lane l of step q = t KS + st: A[16 t + (l & 15)][32 st + 8 (l >> 4) + e])
-__global__ void ddc_prep_kernel(const float* A32, _Float16* afrag, int NT, int KS) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= NT * KS * 64) return;
-  const int q = i >> 6, l = i & 63, t = q / KS, st = q - t * KS;
-  const float* row = A32 + (size_t)(16 * t + (l & 15)) * (32 * KS) + 32 * st + 8 * (l >> 4);
-  _Float16* hi = afrag + ((size_t)q * 2 + 0) * 512 + 8 * l;
-  _Float16* lo = afrag + ((size_t)q * 2 + 1) * 512 + 8 * l;
-  for (int e = 0; e < 8; ++e) {
-    const MmHL p = mm_split(row[e]);
-    hi[e] = p.hi;
-    lo[e] = p.lo;
-  }
-}
-
-// the new history: the last HL samples of (old history, the call's n samples)
-template <bool U8>
-__global__ void ddc_hist_kernel(const void* iq, const void* hold, void* hnew, int64_t n, int HL) {
-  using PT = std::conditional_t<U8, uint16_t, float2>;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= HL) return;
-  const int64_t k = n - HL + i;
-  reinterpret_cast<PT*>(hnew)[i] = k >= 0 ? reinterpret_cast<const PT*>(iq)[k] : reinterpret_cast<const PT*>(hold)[HL + k];
-}
 
 template <int CB, bool U8, bool ALDS>
 __global__ __launch_bounds__(64 * DDC_WAVES) void ddc_mma_kernel(const DdcArgs P) {
@@ -141,34 +116,22 @@ __global__ __launch_bounds__(64 * DDC_WAVES) void ddc_mma_kernel(const DdcArgs P
         }
     } else {
       // the seam and the call's end: complex samples one by one, each from the history
-      // (elements -hl2 .. -1) or the buffer (0 .. n2 - 1); a descriptor reads 0 past its range,
-      // so the two loads are OR-ed.  An element below a range gets an offset past it instead
-      // (off): a negative offset must not reach the instruction -- the compiler merges the two
-      // adjacent 8-byte loads of a chunk into one 16-byte load (or moves the + 2 into the
-      // immediate-offset field), and the range check does not wrap: a load that starts below
-      // the range and ends inside it read 0 for the part inside
+      // (elements -hl2 .. -1) or the buffer (0 .. n2 - 1): the seam load of sdr_stream.h, in
+      // element units
       const int64_t be = e0 > 0 ? e0 : 0;
       const int64_t left = P.n2 - be;
-      const __amdgpu_buffer_rsrc_t ri = mm_rsrc(iqb + be * ES, (left < (1 << 22) ? left : (1 << 22)) * ES);
-      const __amdgpu_buffer_rsrc_t rh = mm_rsrc(P.hist, (int64_t)hl2 * ES);
-      const int d0 = (int)(e0 - be);                // <= 0
-      const int h0 = e0 > 0 ? (1 << 28) : (int)(e0 + hl2);   // >= -2; past the seam: outside the history's range
-      auto off = [](int e) { return e < 0 ? 0x7ffffff0 : e * ES; };
+      const Seam<ES> seam{mm_rsrc(iqb + be * ES, (left < (1 << 22) ? left : (1 << 22)) * ES), mm_rsrc(P.hist, (int64_t)hl2 * ES),
+                        (int)(e0 - be),                                 // <= 0
+                        e0 > 0 ? (1 << 28) : (int)(e0 + hl2)};          // >= -2; past the seam: outside the history's range
 #pragma unroll
       for (int j = 0; j < DDC_NQ_MAX; ++j)
         if (j < nq) {
           const int c = 4 * (l + 64 * j);
           if constexpr (U8) {
-            const uint32_t a0 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(ri, off(d0 + c), 0, 0) |
-                                (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(rh, off(h0 + c), 0, 0);
-            const uint32_t a1 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(ri, off(d0 + c + 2), 0, 0) |
-                                (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(rh, off(h0 + c + 2), 0, 0);
+            const uint32_t a0 = seam.template load<2>(c), a1 = seam.template load<2, 2>(c);
             v[j] = (a0 & 0xffffu) | (a1 << 16);
           } else {
-            const u2v a0 = __builtin_amdgcn_raw_buffer_load_b64(ri, off(d0 + c), 0, 0) |
-                           __builtin_amdgcn_raw_buffer_load_b64(rh, off(h0 + c), 0, 0);
-            const u2v a1 = __builtin_amdgcn_raw_buffer_load_b64(ri, off(d0 + c + 2), 0, 0) |
-                           __builtin_amdgcn_raw_buffer_load_b64(rh, off(h0 + c + 2), 0, 0);
+            const u2v a0 = seam.template load<8>(c), a1 = seam.template load<8, 2>(c);
             v[j] = u4v{a0.x, a0.y, a1.x, a1.y};
           }
         }
@@ -270,9 +233,7 @@ struct sdr_ddc {
   std::vector<uint32_t> inc;
   _Float16* afrag = nullptr;
   uint32_t* dinc = nullptr;
-  void* hist[2] = {nullptr, nullptr};   // the T - 1 samples before the next call (hist[cur]) and the slot the next call fills
-  size_t hbytes = 0;
-  int cur = 0;
+  StreamHist hist;                      // the T - 1 samples before the next call
   int64_t pos = 0;
 };
 
@@ -289,8 +250,7 @@ int sdr_ddc_create(sdr_ctx* c, int nch, const double* freq, const double* b, int
     return fail(SDR_EINVAL, "sdr_ddc_create: decim=%d outside [1, %d]", decim, SDR_DDC_MAX_DECIM);
   if (iq_dtype != SDR_IQ_F32 && iq_dtype != SDR_IQ_U8) return fail(SDR_EINVAL, "sdr_ddc_create: bad iq_dtype %d", iq_dtype);
   if (freq == nullptr || b == nullptr) return fail(SDR_EINVAL, "sdr_ddc_create: freq or taps pointer is NULL");
-  for (int j = 0; j < taps; ++j)
-    if (!std::isfinite(b[j])) return fail(SDR_EINVAL, "sdr_ddc_create: tap %d is not finite", j);
+  TRY(taps_finite(b, taps, "sdr_ddc_create"));
   for (int ch = 0; ch < nch; ++ch)
     if (!std::isfinite(freq[ch]) || std::fabs(freq[ch]) > 0.5)
       return fail(SDR_EINVAL, "sdr_ddc_create: freq[%d]=%g is not a finite value in [-0.5, 0.5] cycles/sample", ch, freq[ch]);
@@ -311,7 +271,6 @@ int sdr_ddc_create(sdr_ctx* c, int nch, const double* freq, const double* b, int
   // inc = rint(nu 2^32) mod 2^32; the complex taps g_c[j] = h[j] exp(+i 2 pi phi_c(j)) in f64
   d->inc.assign(8 * d->NT, 0u);
   std::vector<float> A((size_t)rows * Kp, 0.f);
-  const double two_pi = 6.283185307179586476925286766559;
   for (int ch = 0; ch < nch; ++ch) {
     const uint32_t inc = (uint32_t)(uint64_t)(int64_t)std::nearbyint(freq[ch] * 4294967296.0);
     d->inc[ch] = inc;
@@ -327,31 +286,18 @@ int sdr_ddc_create(sdr_ctx* c, int nch, const double* freq, const double* b, int
       aim[k + 1] = (float)gr;
     }
   }
-  const int es = iq_dtype == SDR_IQ_U8 ? 1 : 4;
-  d->hbytes = std::max<size_t>(16, (size_t)2 * (taps - 1) * es);
+  const bool u8 = iq_dtype == SDR_IQ_U8;
   float* dA = nullptr;
-  const size_t fbytes = (size_t)d->NT * d->KS * 2 * 512 * sizeof(_Float16);
-  hipError_t e = hipMalloc(&dA, A.size() * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d->afrag, fbytes);
-  if (e == hipSuccess) e = hipMalloc(&d->dinc, d->inc.size() * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(&d->hist[0], d->hbytes);
-  if (e == hipSuccess) e = hipMalloc(&d->hist[1], d->hbytes);
-  if (e == hipSuccess) e = hipMemcpyAsync(dA, A.data(), A.size() * sizeof(float), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(d->dinc, d->inc.data(), d->inc.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    const int nthr = d->NT * d->KS * 64;
-    ddc_prep_kernel<<<(nthr + 255) / 256, 256, 0, c->stream>>>(dA, d->afrag, d->NT, d->KS);
-    e = hipGetLastError();
-  }
-  // the u8 zero level is 128; a zero history is 0 for f32
-  if (e == hipSuccess) e = hipMemsetAsync(d->hist[0], iq_dtype == SDR_IQ_U8 ? 128 : 0, d->hbytes, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(d->hist[1], iq_dtype == SDR_IQ_U8 ? 128 : 0, d->hbytes, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  hipError_t e = upload(&dA, A.data(), A.size(), c->stream);
+  if (e == hipSuccess) e = upload(&d->dinc, d->inc.data(), d->inc.size(), c->stream);
+  if (e == hipSuccess) e = hipMalloc(&d->afrag, (size_t)d->NT * d->KS * 2 * 512 * sizeof(_Float16));
+  if (e == hipSuccess) e = mm_prep(dA, d->afrag, d->NT, d->KS, c->stream);
+  if (e == hipSuccess) e = d->hist.alloc((size_t)2 * (taps - 1) * (u8 ? 1 : 4), u8 ? 128 : 0, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (the host vectors are read until here)
   (void)hipFree(dA);
   if (e != hipSuccess) {
     sdr_ddc_destroy(d);
-    return fail(e == hipErrorOutOfMemory ? SDR_ENOMEM : SDR_EHIP, "sdr_ddc_create: %s", hipGetErrorString(e));
+    return create_failed(e, "sdr_ddc_create");
   }
   *out = d;
   return SDR_OK;
@@ -362,8 +308,7 @@ void sdr_ddc_destroy(sdr_ddc* d) {
   if (d->ctx != nullptr && set_dev(d->ctx) == SDR_OK) (void)hipStreamSynchronize(d->ctx->stream);
   (void)hipFree(d->afrag);
   (void)hipFree(d->dinc);
-  (void)hipFree(d->hist[0]);
-  (void)hipFree(d->hist[1]);
+  d->hist.free();
   delete d;
 }
 
@@ -378,7 +323,7 @@ int sdr_ddc_reset(sdr_ddc* d, int64_t position) {
   if (position < 0 || position % d->D != 0)
     return fail(SDR_EINVAL, "sdr_ddc_reset: position=%lld must be >= 0 and a multiple of decim=%d", (long long)position, d->D);
   TRY(set_dev(d->ctx));
-  HIP_TRY(hipMemsetAsync(d->hist[d->cur], d->dtype == SDR_IQ_U8 ? 128 : 0, d->hbytes, d->ctx->stream));
+  HIP_TRY(d->hist.reset(d->ctx->stream));
   d->pos = position;
   return SDR_OK;
 }
@@ -389,17 +334,8 @@ int sdr_ddc_position(sdr_ddc* d, int64_t* position) {
   return SDR_OK;
 }
 
-static int ddc_check_call(sdr_ddc* d, const void* iq, int64_t n, const float* out, int64_t out_stride, const char* what) {
-  if (d == nullptr) return fail(SDR_EINVAL, "%s: object is NULL", what);
-  if (iq == nullptr || out == nullptr) return fail(SDR_EINVAL, "%s: iq or out is NULL", what);
-  if (n < 1 || n % d->D != 0) return fail(SDR_EINVAL, "%s: n=%lld must be >= 1 and a multiple of decim=%d", what, (long long)n, d->D);
-  if (out_stride < n / d->D)
-    return fail(SDR_EINVAL, "%s: out_stride=%lld < n/decim=%lld", what, (long long)out_stride, (long long)(n / d->D));
-  return SDR_OK;
-}
-
 int sdr_ddc_process_dev(sdr_ddc* d, const void* iq, int64_t n, float* out, int64_t out_stride) {
-  TRY(ddc_check_call(d, iq, n, out, out_stride, "sdr_ddc_process_dev"));
+  TRY(decim_check_call(d, iq, n, out, out_stride, "sdr_ddc_process_dev"));
   const bool u8 = d->dtype == SDR_IQ_U8;
   if (((uintptr_t)iq & (u8 ? 1 : 7)) != 0 || ((uintptr_t)out & 7) != 0)
     return fail(SDR_EINVAL, "sdr_ddc_process_dev: iq must be aligned to one complex sample (%d B) and out to 8 B", u8 ? 2 : 8);
@@ -407,7 +343,7 @@ int sdr_ddc_process_dev(sdr_ddc* d, const void* iq, int64_t n, float* out, int64
   TRY(set_dev(c));
   DdcArgs P;
   P.iq = iq;
-  P.hist = d->hist[d->cur];
+  P.hist = d->hist.current();
   P.afrag = d->afrag;
   P.inc = d->dinc;
   P.out = out;
@@ -445,34 +381,19 @@ int sdr_ddc_process_dev(sdr_ddc* d, const void* iq, int64_t n, float* out, int64
   }
 #undef DDC_LAUNCH
   HIP_TRY(hipGetLastError());
-  const int HL = d->T - 1;
-  if (HL > 0) {
-    void* hn = d->hist[d->cur ^ 1];
-    if (u8) ddc_hist_kernel<true><<<(HL + 255) / 256, 256, 0, c->stream>>>(iq, d->hist[d->cur], hn, n, HL);
-    else ddc_hist_kernel<false><<<(HL + 255) / 256, 256, 0, c->stream>>>(iq, d->hist[d->cur], hn, n, HL);
-    HIP_TRY(hipGetLastError());
-    d->cur ^= 1;
-  }
+  if (u8) HIP_TRY(d->hist.advance<uint16_t>(c->stream, iq, n, 0, 1, d->T - 1));
+  else HIP_TRY(d->hist.advance<float2>(c->stream, iq, n, 0, 1, d->T - 1));
   d->pos += n;
   return SDR_OK;
 }
 
 int sdr_ddc_run(sdr_ddc* d, const void* iq_host, int64_t n, float* out_host, int64_t out_stride) {
-  TRY(ddc_check_call(d, iq_host, n, out_host, out_stride, "sdr_ddc_run"));
+  TRY(decim_check_call(d, iq_host, n, out_host, out_stride, "sdr_ddc_run"));
   sdr_ctx* c = d->ctx;
   TRY(set_dev(c));
-  const size_t es = d->dtype == SDR_IQ_U8 ? 1 : 4;
-  const int64_t M = n / d->D;
-  void* din = nullptr;
-  float* dout = nullptr;
-  TRY(scratch(c, S_IN, (size_t)2 * n * es, &din));
-  TRY(scratch(c, S_OUT, (size_t)d->nch * M * 2 * sizeof(float), (void**)&dout));
-  HIP_TRY(hipMemcpyAsync(din, iq_host, (size_t)2 * n * es, hipMemcpyHostToDevice, c->stream));
-  TRY(sdr_ddc_process_dev(d, din, n, dout, M));
-  HIP_TRY(hipMemcpy2DAsync(out_host, (size_t)out_stride * 8, dout, (size_t)M * 8, (size_t)M * 8, (size_t)d->nch,
-                           hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return SDR_OK;
+  const size_t es = d->dtype == SDR_IQ_U8 ? 2 : 8, M = (size_t)(n / d->D);
+  return run_staged(c, iq_host, {1, (size_t)n * es, 0}, out_host, {(size_t)d->nch, M * 8, (size_t)out_stride * 8},
+                    [&](void* din, void* dout) { return sdr_ddc_process_dev(d, din, n, (float*)dout, (int64_t)M); });
 }
 
 }  // extern "C"

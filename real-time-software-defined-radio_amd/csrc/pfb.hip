@@ -18,8 +18,8 @@
 // 1 where the window's buffers take more than half a compute unit's LDS).  Per window:
 //   stage  the (W - 1) D + P M complex inputs into LDS as f32 pairs, one buffer load each -- the
 //          input is read from HBM once per call, whatever nch is.  Windows that reach below the
-//          call's first sample OR the object's history (the T - 1 samples before the call) in
-//          through a second range-checked descriptor; no access leaves either buffer;
+//          call's first sample read across the seam to the object's history (the T - 1 samples
+//          before the call; sdr_stream.h); no access leaves either buffer;
 //   fold   in f32 on the vector units: a thread runs the FMA chain over q for four (n, p) pairs
 //          at a time, the taps and the samples from LDS, and writes u as f16 hi / lo planes, one
 //          row of 32 KS (+ 8) halfs per output time -- u never goes to HBM;
@@ -44,6 +44,7 @@
 #include "sdr_ctx.h"
 #include "sdr_launch.h"
 #include "sdr_mma.h"
+#include "sdr_stream.h"
 
 using namespace sdrint;
 
@@ -56,8 +57,6 @@ constexpr size_t PFB_LDS_ALDS = 64 * 1024;         // A fragments stay in LDS wh
 constexpr size_t PFB_LDS_WINDOW = 80 * 1024;       // the full window while its buffers fit this: two workgroups per CU
 constexpr size_t PFB_LDS_MAX = 160 * 1024;         // LDS of a gfx950 compute unit
 static_assert(16 * PFB_CB == SDR_PFB_WINDOW, "the window the header names");
-
-typedef uint32_t u2v __attribute__((ext_vector_type(2)));
 
 inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
@@ -116,31 +115,6 @@ static __device__ __forceinline__ int pfb_mod(int v, int M, float invM) {
   return pfb_divmod(v, M, invM, &q);
 }
 
-// A32: [16 NT][32 KS] f32 rows -> fragments (lane l of step q = t KS + st: A[16 t + (l & 15)][32 st + 8 (l >> 4) + e])
-__global__ void pfb_prep_kernel(const float* A32, _Float16* afrag, int NT, int KS) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= NT * KS * 64) return;
-  const int q = i >> 6, l = i & 63, t = q / KS, st = q - t * KS;
-  const float* row = A32 + (size_t)(16 * t + (l & 15)) * (32 * KS) + 32 * st + 8 * (l >> 4);
-  _Float16* hi = afrag + ((size_t)q * 2 + 0) * 512 + 8 * l;
-  _Float16* lo = afrag + ((size_t)q * 2 + 1) * 512 + 8 * l;
-  for (int e = 0; e < 8; ++e) {
-    const MmHL p = mm_split(row[e]);
-    hi[e] = p.hi;
-    lo[e] = p.lo;
-  }
-}
-
-// the new history: the last HL samples of (old history, the call's n samples)
-template <bool U8>
-__global__ void pfb_hist_kernel(const void* iq, const void* hold, void* hnew, int64_t n, int HL) {
-  using PT = std::conditional_t<U8, uint16_t, float2>;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= HL) return;
-  const int64_t k = n - HL + i;
-  reinterpret_cast<PT*>(hnew)[i] = k >= 0 ? reinterpret_cast<const PT*>(iq)[k] : reinterpret_cast<const PT*>(hold)[HL + k];
-}
-
 template <int CB, bool U8, bool ALDS>
 __global__ __launch_bounds__(PFB_THREADS) void pfb_mma_kernel(const PfbArgs P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char pfb_lds[];
@@ -193,41 +167,30 @@ __global__ __launch_bounds__(PFB_THREADS) void pfb_mma_kernel(const PfbArgs P) {
   };
 
   for (int64_t p = blockIdx.x; p < P.passes; p += gridDim.x) {
-    // ---- stage: x_s[i] = sample sb + i of the call (0 = its first), sb = m0 D - (P M - 1).  A
-    // descriptor reads 0 past its range; an index below a range gets an offset past it instead:
-    // a negative offset must not reach the instruction (the range check does not wrap)
+    // ---- stage: x_s[i] = sample sb + i of the call (0 = its first), sb = m0 D - (P M - 1): the
+    // seam load of sdr_stream.h, in samples
     const int64_t m0 = p * W;
     const int64_t sb = m0 * D - (PM - 1);
     const int64_t be = sb > 0 ? sb : 0;
     const int64_t left = P.n - be;                  // >= 1: m0 D < n
-    const __amdgpu_buffer_rsrc_t ri = mm_rsrc(iqb + be * ES, (left < L ? left : L) * ES);
-    const int d0 = (int)(sb - be);                  // <= 0
-    auto off = [](int e) { return e < 0 ? 0x7ffffff0 : e * ES; };
+    Seam<ES> seam;
+    seam.in = mm_rsrc(iqb + be * ES, (left < L ? left : L) * ES);
+    seam.d0 = (int)(sb - be);                         // <= 0
     auto conv = [](uint32_t v) {
       return float2{((float)(v & 255u) - 128.f) * (1.f / 128.f), ((float)((v >> 8) & 255u) - 128.f) * (1.f / 128.f)};
     };
     if (sb < 0 && hl > 0) {                         // (uniform) the window reaches into the history
-      const __amdgpu_buffer_rsrc_t rh = mm_rsrc(P.hist, (int64_t)hl * ES);
-      const int h0 = (int)(sb + hl);                // the history's index of x_s[0]; below 0 where P M > T
+      seam.hist = mm_rsrc(P.hist, (int64_t)hl * ES);
+      seam.h0 = (int)(sb + hl);                       // the history's index of x_s[0]; below 0 where P M > T
       for (int i = tid; i < L; i += PFB_THREADS) {
-        if constexpr (U8) {
-          const uint32_t v = (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(ri, off(d0 + i), 0, 0) |
-                             (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(rh, off(h0 + i), 0, 0);
-          x_s[i] = conv(v & 0xffffu);
-        } else {
-          const u2v v = __builtin_amdgcn_raw_buffer_load_b64(ri, off(d0 + i), 0, 0) |
-                        __builtin_amdgcn_raw_buffer_load_b64(rh, off(h0 + i), 0, 0);
-          x_s[i] = __builtin_bit_cast(float2, v);
-        }
+        if constexpr (U8) x_s[i] = conv(seam.template load<ES>(i) & 0xffffu);
+        else x_s[i] = __builtin_bit_cast(float2, seam.template load<ES>(i));
       }
     } else {
 #pragma unroll 4
       for (int i = tid; i < L; i += PFB_THREADS) {
-        if constexpr (U8) {
-          x_s[i] = conv((uint32_t)__builtin_amdgcn_raw_buffer_load_b16(ri, off(d0 + i), 0, 0) & 0xffffu);
-        } else {
-          x_s[i] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(ri, off(d0 + i), 0, 0));
-        }
+        if constexpr (U8) x_s[i] = conv(seam.template load_in<ES>(i) & 0xffffu);
+        else x_s[i] = __builtin_bit_cast(float2, seam.template load_in<ES>(i));
       }
     }
     __syncthreads();                                // x_s complete; every wave is done with the previous u
@@ -386,9 +349,7 @@ struct sdr_pfb {
   _Float16* afrag = nullptr;
   float2* rot = nullptr;
   int* dbin = nullptr;
-  void* hist[2] = {nullptr, nullptr};   // the T - 1 samples before the next call (hist[cur]) and the slot the next call fills
-  size_t hbytes = 0;
-  int cur = 0;
+  StreamHist hist;                      // the T - 1 samples before the next call
   int64_t pos = 0;
   int grid = 0;                         // resident workgroups of its launch (from the first call on)
 };
@@ -408,8 +369,7 @@ int sdr_pfb_create(sdr_ctx* c, int nbins, int nch, const int* bin, const double*
     return fail(SDR_EINVAL, "sdr_pfb_create: decim=%d outside [1, %d]", decim, SDR_PFB_MAX_DECIM);
   if (iq_dtype != SDR_IQ_F32 && iq_dtype != SDR_IQ_U8) return fail(SDR_EINVAL, "sdr_pfb_create: bad iq_dtype %d", iq_dtype);
   if (bin == nullptr || b == nullptr) return fail(SDR_EINVAL, "sdr_pfb_create: bin or taps pointer is NULL");
-  for (int j = 0; j < taps; ++j)
-    if (!std::isfinite(b[j])) return fail(SDR_EINVAL, "sdr_pfb_create: tap %d is not finite", j);
+  TRY(taps_finite(b, taps, "sdr_pfb_create"));
   for (int ch = 0; ch < nch; ++ch)
     if (bin[ch] < 0 || bin[ch] >= nbins)
       return fail(SDR_EINVAL, "sdr_pfb_create: bin[%d]=%d outside [0, nbins=%d)", ch, bin[ch], nbins);
@@ -431,7 +391,6 @@ int sdr_pfb_create(sdr_ctx* c, int nbins, int nch, const int* bin, const double*
   // the full window where its buffers fit the LDS without the A fragments, else one column block
   d->CB = pfb_layout(M, d->NT, d->PM, decim, d->KS, PFB_CB, 0).total <= PFB_LDS_WINDOW ? PFB_CB : 1;
   const int Kp = 32 * d->KS, rows = 16 * d->NT;
-  const double two_pi = 6.283185307179586476925286766559;
   // the DFT rows exp(+2 pi i (bin p mod M) / M) and the rotations exp(-2 pi i t / M), in f64
   std::vector<float> A((size_t)rows * Kp, 0.f);
   for (int ch = 0; ch < nch; ++ch) {
@@ -455,33 +414,20 @@ int sdr_pfb_create(sdr_ctx* c, int nbins, int nch, const int* bin, const double*
   for (int j = 0; j < taps; ++j) h32[j] = (float)b[j];
   std::vector<int> bins(8 * d->NT, 0);
   for (int ch = 0; ch < nch; ++ch) bins[ch] = bin[ch];
-  const int es = iq_dtype == SDR_IQ_U8 ? 2 : 8;
-  d->hbytes = std::max<size_t>(16, (size_t)(taps - 1) * es);
+  const bool u8 = iq_dtype == SDR_IQ_U8;
   float* dA = nullptr;
-  hipError_t e = hipMalloc(&dA, A.size() * sizeof(float));
+  hipError_t e = upload(&dA, A.data(), A.size(), c->stream);
+  if (e == hipSuccess) e = upload(&d->rot, rot.data(), rot.size(), c->stream);
+  if (e == hipSuccess) e = upload(&d->taps, h32.data(), h32.size(), c->stream);
+  if (e == hipSuccess) e = upload(&d->dbin, bins.data(), bins.size(), c->stream);
   if (e == hipSuccess) e = hipMalloc(&d->afrag, d->abytes);
-  if (e == hipSuccess) e = hipMalloc(&d->rot, rot.size() * sizeof(float2));
-  if (e == hipSuccess) e = hipMalloc(&d->taps, h32.size() * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d->dbin, bins.size() * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(&d->hist[0], d->hbytes);
-  if (e == hipSuccess) e = hipMalloc(&d->hist[1], d->hbytes);
-  if (e == hipSuccess) e = hipMemcpyAsync(dA, A.data(), A.size() * sizeof(float), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d->rot, rot.data(), rot.size() * sizeof(float2), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d->taps, h32.data(), h32.size() * sizeof(float), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d->dbin, bins.data(), bins.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    const int nthr = d->NT * d->KS * 64;
-    pfb_prep_kernel<<<(nthr + 255) / 256, 256, 0, c->stream>>>(dA, d->afrag, d->NT, d->KS);
-    e = hipGetLastError();
-  }
-  // the u8 zero level is 128; a zero history is 0 for f32
-  if (e == hipSuccess) e = hipMemsetAsync(d->hist[0], iq_dtype == SDR_IQ_U8 ? 128 : 0, d->hbytes, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(d->hist[1], iq_dtype == SDR_IQ_U8 ? 128 : 0, d->hbytes, c->stream);
+  if (e == hipSuccess) e = mm_prep(dA, d->afrag, d->NT, d->KS, c->stream);
+  if (e == hipSuccess) e = d->hist.alloc((size_t)(taps - 1) * (u8 ? 2 : 8), u8 ? 128 : 0, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (the host vectors are read until here)
   (void)hipFree(dA);
   if (e != hipSuccess) {
     sdr_pfb_destroy(d);
-    return fail(e == hipErrorOutOfMemory ? SDR_ENOMEM : SDR_EHIP, "sdr_pfb_create: %s", hipGetErrorString(e));
+    return create_failed(e, "sdr_pfb_create");
   }
   *out = d;
   return SDR_OK;
@@ -494,8 +440,7 @@ void sdr_pfb_destroy(sdr_pfb* d) {
   (void)hipFree(d->rot);
   (void)hipFree(d->taps);
   (void)hipFree(d->dbin);
-  (void)hipFree(d->hist[0]);
-  (void)hipFree(d->hist[1]);
+  d->hist.free();
   delete d;
 }
 
@@ -504,7 +449,7 @@ int sdr_pfb_reset(sdr_pfb* d, int64_t position) {
   if (position < 0 || position % d->D != 0)
     return fail(SDR_EINVAL, "sdr_pfb_reset: position=%lld must be >= 0 and a multiple of decim=%d", (long long)position, d->D);
   TRY(set_dev(d->ctx));
-  HIP_TRY(hipMemsetAsync(d->hist[d->cur], d->dtype == SDR_IQ_U8 ? 128 : 0, d->hbytes, d->ctx->stream));
+  HIP_TRY(d->hist.reset(d->ctx->stream));
   d->pos = position;
   return SDR_OK;
 }
@@ -515,17 +460,8 @@ int sdr_pfb_position(sdr_pfb* d, int64_t* position) {
   return SDR_OK;
 }
 
-static int pfb_check_call(sdr_pfb* d, const void* iq, int64_t n, const float* out, int64_t out_stride, const char* what) {
-  if (d == nullptr) return fail(SDR_EINVAL, "%s: object is NULL", what);
-  if (iq == nullptr || out == nullptr) return fail(SDR_EINVAL, "%s: iq or out is NULL", what);
-  if (n < 1 || n % d->D != 0) return fail(SDR_EINVAL, "%s: n=%lld must be >= 1 and a multiple of decim=%d", what, (long long)n, d->D);
-  if (out_stride < n / d->D)
-    return fail(SDR_EINVAL, "%s: out_stride=%lld < n/decim=%lld", what, (long long)out_stride, (long long)(n / d->D));
-  return SDR_OK;
-}
-
 int sdr_pfb_process_dev(sdr_pfb* d, const void* iq, int64_t n, float* out, int64_t out_stride) {
-  TRY(pfb_check_call(d, iq, n, out, out_stride, "sdr_pfb_process_dev"));
+  TRY(decim_check_call(d, iq, n, out, out_stride, "sdr_pfb_process_dev"));
   const bool u8 = d->dtype == SDR_IQ_U8;
   if (((uintptr_t)iq & (u8 ? 1 : 7)) != 0 || ((uintptr_t)out & 7) != 0)
     return fail(SDR_EINVAL, "sdr_pfb_process_dev: iq must be aligned to one complex sample (%d B) and out to 8 B", u8 ? 2 : 8);
@@ -538,7 +474,7 @@ int sdr_pfb_process_dev(sdr_pfb* d, const void* iq, int64_t n, float* out, int64
   if (lay.total > PFB_LDS_MAX) return fail(SDR_EHIP, "sdr_pfb_process_dev: %zu B of LDS", lay.total);   // (not inside the limits)
   PfbArgs P;
   P.iq = iq;
-  P.hist = d->hist[d->cur];
+  P.hist = d->hist.current();
   P.taps = d->taps;
   P.afrag = d->afrag;
   P.rot = d->rot;
@@ -597,34 +533,19 @@ int sdr_pfb_process_dev(sdr_pfb* d, const void* iq, int64_t n, float* out, int64
 #undef PFB_LAUNCH
 #undef PFB_LAUNCH1
   HIP_TRY(hipGetLastError());
-  const int HL = d->T - 1;
-  if (HL > 0) {
-    void* hn = d->hist[d->cur ^ 1];
-    if (u8) pfb_hist_kernel<true><<<(HL + 255) / 256, 256, 0, c->stream>>>(iq, d->hist[d->cur], hn, n, HL);
-    else pfb_hist_kernel<false><<<(HL + 255) / 256, 256, 0, c->stream>>>(iq, d->hist[d->cur], hn, n, HL);
-    HIP_TRY(hipGetLastError());
-    d->cur ^= 1;
-  }
+  if (u8) HIP_TRY(d->hist.advance<uint16_t>(c->stream, iq, n, 0, 1, d->T - 1));
+  else HIP_TRY(d->hist.advance<float2>(c->stream, iq, n, 0, 1, d->T - 1));
   d->pos += n;
   return SDR_OK;
 }
 
 int sdr_pfb_run(sdr_pfb* d, const void* iq_host, int64_t n, float* out_host, int64_t out_stride) {
-  TRY(pfb_check_call(d, iq_host, n, out_host, out_stride, "sdr_pfb_run"));
+  TRY(decim_check_call(d, iq_host, n, out_host, out_stride, "sdr_pfb_run"));
   sdr_ctx* c = d->ctx;
   TRY(set_dev(c));
-  const size_t es = d->dtype == SDR_IQ_U8 ? 1 : 4;
-  const int64_t M = n / d->D;
-  void* din = nullptr;
-  float* dout = nullptr;
-  TRY(scratch(c, S_IN, (size_t)2 * n * es, &din));
-  TRY(scratch(c, S_OUT, (size_t)d->nch * M * 2 * sizeof(float), (void**)&dout));
-  HIP_TRY(hipMemcpyAsync(din, iq_host, (size_t)2 * n * es, hipMemcpyHostToDevice, c->stream));
-  TRY(sdr_pfb_process_dev(d, din, n, dout, M));
-  HIP_TRY(hipMemcpy2DAsync(out_host, (size_t)out_stride * 8, dout, (size_t)M * 8, (size_t)M * 8, (size_t)d->nch,
-                           hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return SDR_OK;
+  const size_t es = d->dtype == SDR_IQ_U8 ? 2 : 8, M = (size_t)(n / d->D);
+  return run_staged(c, iq_host, {1, (size_t)n * es, 0}, out_host, {(size_t)d->nch, M * 8, (size_t)out_stride * 8},
+                    [&](void* din, void* dout) { return sdr_pfb_process_dev(d, din, n, (float*)dout, (int64_t)M); });
 }
 
 }  // extern "C"

@@ -15,18 +15,16 @@
 //   stage  the tile's input span, samples S0 - (P - 1) .. S0 + To D / U - 1, into LDS.  Where the
 //          span lies inside the caller's row: 16-byte buffer loads from the 16-byte boundary at or
 //          below its first sample (the LDS copy starts `sh` samples early).  At the row's two ends:
-//          sample by sample, the caller's row and the object's history (the P - 1 samples before
-//          the call) through two range-checked descriptors, OR-ed -- a descriptor reads 0 past its
-//          range, and an index below a range is turned into an offset past it.  No access leaves
-//          the row's n samples or the history: the gaps between rows are never read;
+//          sample by sample across the seam between the object's history (the P - 1 samples before
+//          the call) and the caller's row (sdr_stream.h).  No access leaves the row's n samples or
+//          the history: the gaps between rows are never read;
 //   FMA    item (c, p), p < U, owns the R outputs m' = (c R + k) U + p, k < R, of the tile: they
 //          share the phase r = (p D) mod U, so one tap read per q serves R outputs and both
 //          components; their samples are D apart.  The taps sit in LDS as g[q U + r]: neighbouring
 //          lanes read neighbouring taps where D mod U = 1, and samples about D / U apart.  Complex
 //          samples are 8-byte LDS reads.  (No skew of the staging: where 2 D / U dwords is a
 //          multiple of 64 the lanes' sample reads share a bank -- DESIGN.md §10.)
-// The history update is a second launch: the last P - 1 samples of (old history, the call's rows)
-// into the other of two buffers.
+// The history update is a second launch (sdr_stream.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +35,7 @@
 
 #include "sdr_ctx.h"
 #include "sdr_mma.h"
+#include "sdr_stream.h"
 
 using namespace sdrint;
 
@@ -45,8 +44,6 @@ namespace {
 constexpr int RSMP_THREADS = 256;
 constexpr size_t RSMP_LDS = 64 * 1024;             // taps + staging of a workgroup: two per compute unit at the least
 constexpr int RSMP_MAX_GRID = 1 << 20;             // tiles per row beyond this are looped over
-
-typedef uint32_t u2v __attribute__((ext_vector_type(2)));
 
 inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
@@ -97,25 +94,13 @@ __global__ __launch_bounds__(RSMP_THREADS) void rsmp_kernel(const RsmpArgs A) {
       for (int j = tid; j < nq; j += RSMP_THREADS)
         reinterpret_cast<u4v*>(x_s)[j] = __builtin_amdgcn_raw_buffer_load_b128(r, 16 * j, 0, 0);
     } else {
-      // a negative offset must not reach the instruction (the range check does not wrap)
+      // the seam load of sdr_stream.h, in samples
       const int64_t be = sb > 0 ? sb : 0;
       const int64_t left = A.n - be;                // >= 1
-      const __amdgpu_buffer_rsrc_t ri = mm_rsrc(rowb + be * ES, (left < L ? left : L) * ES);
-      const __amdgpu_buffer_rsrc_t rh = mm_rsrc(hb, (int64_t)HL * ES);
-      const int d0 = (int)(sb - be);                // <= 0
-      const int h0 = S0 < HL ? (int)S0 : HL;        // the history's index of x_s[sh]: sb + HL; from HL on outside it
-      auto off = [](int e) { return e < 0 ? 0x7ffffff0 : e * ES; };
-      for (int i = tid; i < L; i += RSMP_THREADS) {
-        if constexpr (E == 2) {
-          const u2v v = __builtin_amdgcn_raw_buffer_load_b64(ri, off(d0 + i), 0, 0) |
-                        __builtin_amdgcn_raw_buffer_load_b64(rh, off(h0 + i), 0, 0);
-          x_s[sh + i] = __builtin_bit_cast(float2, v);
-        } else {
-          const uint32_t v = __builtin_amdgcn_raw_buffer_load_b32(ri, off(d0 + i), 0, 0) |
-                             __builtin_amdgcn_raw_buffer_load_b32(rh, off(h0 + i), 0, 0);
-          x_s[sh + i] = __builtin_bit_cast(float, v);
-        }
-      }
+      const Seam<ES> seam{mm_rsrc(rowb + be * ES, (left < L ? left : L) * ES), mm_rsrc(hb, (int64_t)HL * ES),
+                        (int)(sb - be),             // <= 0
+                        S0 < HL ? (int)S0 : HL};    // the history's index of x_s[sh]: sb + HL; from HL on outside it
+      for (int i = tid; i < L; i += RSMP_THREADS) x_s[sh + i] = __builtin_bit_cast(ST, seam.template load<ES>(i));
     }
     __syncthreads();                                // x_s (and, the first time, the taps) complete
 
@@ -168,19 +153,6 @@ __global__ __launch_bounds__(RSMP_THREADS) void rsmp_kernel(const RsmpArgs A) {
   }
 }
 
-// the new history: the last HL samples of (old history, the call's n samples), every row
-template <int E>
-__global__ void rsmp_hist_kernel(const float* in, const float* hold, float* hnew, int64_t n, int64_t in_stride, int HL) {
-  using ST = std::conditional_t<E == 2, float2, float>;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= HL) return;
-  const int64_t row = blockIdx.y;
-  const int64_t k = n - HL + i;
-  const ST* x = reinterpret_cast<const ST*>(in) + row * in_stride;
-  const ST* ho = reinterpret_cast<const ST*>(hold) + row * HL;
-  reinterpret_cast<ST*>(hnew)[row * HL + i] = k >= 0 ? x[k] : ho[HL + k];
-}
-
 }  // namespace
 
 struct sdr_rsmp {
@@ -189,9 +161,7 @@ struct sdr_rsmp {
   int64_t step = 0;                     // a call's n is a multiple of this: D / gcd(U, D)
   size_t o_xs = 0, lds = 0;
   float* taps = nullptr;
-  float* hist[2] = {nullptr, nullptr};  // the P - 1 samples before the next call, per row (hist[cur]), and the slot the next call fills
-  size_t hbytes = 0;
-  int cur = 0;
+  StreamHist hist;                      // the P - 1 samples before the next call, per row
   int64_t pos = 0;
 };
 
@@ -212,8 +182,7 @@ int sdr_rsmp_create(sdr_ctx* c, int nrows, int elems, const double* b, int taps,
   if ((taps + up - 1) / up > SDR_RSMP_MAX_PHASE_TAPS)
     return fail(SDR_EINVAL, "sdr_rsmp_create: taps=%d at up=%d is more than %d taps per phase", taps, up, SDR_RSMP_MAX_PHASE_TAPS);
   if (b == nullptr) return fail(SDR_EINVAL, "sdr_rsmp_create: taps pointer is NULL");
-  for (int j = 0; j < taps; ++j)
-    if (!std::isfinite(b[j])) return fail(SDR_EINVAL, "sdr_rsmp_create: tap %d is not finite", j);
+  TRY(taps_finite(b, taps, "sdr_rsmp_create"));
   CHECK_CTX(c);
   TRY(set_dev(c));
   sdr_rsmp* d = new (std::nothrow) sdr_rsmp;
@@ -249,17 +218,12 @@ int sdr_rsmp_create(sdr_ctx* c, int nrows, int elems, const double* b, int taps,
   }
   std::vector<float> g32((size_t)d->P * up, 0.f);
   for (int j = 0; j < taps; ++j) g32[j] = (float)((double)up * b[j]);
-  d->hbytes = std::max<size_t>(16, (size_t)nrows * (d->P - 1) * es);
-  hipError_t e = hipMalloc(&d->taps, g32.size() * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d->hist[0], d->hbytes);
-  if (e == hipSuccess) e = hipMalloc(&d->hist[1], d->hbytes);
-  if (e == hipSuccess) e = hipMemcpyAsync(d->taps, g32.data(), g32.size() * sizeof(float), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(d->hist[0], 0, d->hbytes, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(d->hist[1], 0, d->hbytes, c->stream);
+  hipError_t e = upload(&d->taps, g32.data(), g32.size(), c->stream);
+  if (e == hipSuccess) e = d->hist.alloc((size_t)nrows * (d->P - 1) * es, 0, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (the host vector is read until here)
   if (e != hipSuccess) {
     sdr_rsmp_destroy(d);
-    return fail(e == hipErrorOutOfMemory ? SDR_ENOMEM : SDR_EHIP, "sdr_rsmp_create: %s", hipGetErrorString(e));
+    return create_failed(e, "sdr_rsmp_create");
   }
   *out = d;
   return SDR_OK;
@@ -269,15 +233,14 @@ void sdr_rsmp_destroy(sdr_rsmp* d) {
   if (d == nullptr) return;
   if (d->ctx != nullptr && set_dev(d->ctx) == SDR_OK) (void)hipStreamSynchronize(d->ctx->stream);
   (void)hipFree(d->taps);
-  (void)hipFree(d->hist[0]);
-  (void)hipFree(d->hist[1]);
+  d->hist.free();
   delete d;
 }
 
 int sdr_rsmp_reset(sdr_rsmp* d) {
   if (d == nullptr) return fail(SDR_EINVAL, "sdr_rsmp_reset: object is NULL");
   TRY(set_dev(d->ctx));
-  HIP_TRY(hipMemsetAsync(d->hist[d->cur], 0, d->hbytes, d->ctx->stream));
+  HIP_TRY(d->hist.reset(d->ctx->stream));
   d->pos = 0;
   return SDR_OK;
 }
@@ -317,7 +280,7 @@ int sdr_rsmp_process_dev(sdr_rsmp* d, const float* in, int64_t n, int64_t in_str
   TRY(set_dev(c));
   RsmpArgs A;
   A.in = in;
-  A.hist = d->hist[d->cur];
+  A.hist = static_cast<const float*>(d->hist.current());
   A.taps = d->taps;
   A.out = out;
   A.n = n;
@@ -341,15 +304,8 @@ int sdr_rsmp_process_dev(sdr_rsmp* d, const float* in, int64_t n, int64_t in_str
     else rsmp_kernel<1, 2><<<grid, blk, d->lds, c->stream>>>(A);
   }
   HIP_TRY(hipGetLastError());
-  const int HL = d->P - 1;
-  if (HL > 0) {
-    float* hn = d->hist[d->cur ^ 1];
-    const dim3 hg((unsigned)((HL + 255) / 256), (unsigned)d->nrows);
-    if (d->E == 2) rsmp_hist_kernel<2><<<hg, 256, 0, c->stream>>>(in, d->hist[d->cur], hn, n, in_stride, HL);
-    else rsmp_hist_kernel<1><<<hg, 256, 0, c->stream>>>(in, d->hist[d->cur], hn, n, in_stride, HL);
-    HIP_TRY(hipGetLastError());
-    d->cur ^= 1;
-  }
+  if (d->E == 2) HIP_TRY(d->hist.advance<float2>(c->stream, in, n, in_stride, d->nrows, d->P - 1));
+  else HIP_TRY(d->hist.advance<float>(c->stream, in, n, in_stride, d->nrows, d->P - 1));
   d->pos += n;
   return SDR_OK;
 }
@@ -358,19 +314,10 @@ int sdr_rsmp_run(sdr_rsmp* d, const float* in_host, int64_t n, int64_t in_stride
   TRY(rsmp_check_call(d, in_host, n, in_stride, out_host, out_stride, "sdr_rsmp_run"));
   sdr_ctx* c = d->ctx;
   TRY(set_dev(c));
-  const size_t es = 4 * (size_t)d->E;
+  const size_t es = 4 * (size_t)d->E, rows = (size_t)d->nrows;
   const int64_t Mo = n / d->step * (d->U / (d->D / d->step));
-  float* din = nullptr;
-  float* dout = nullptr;
-  TRY(scratch(c, S_IN, (size_t)d->nrows * n * es, (void**)&din));
-  TRY(scratch(c, S_OUT, (size_t)d->nrows * Mo * es, (void**)&dout));
-  HIP_TRY(hipMemcpy2DAsync(din, (size_t)n * es, in_host, (size_t)in_stride * es, (size_t)n * es, (size_t)d->nrows,
-                           hipMemcpyHostToDevice, c->stream));
-  TRY(sdr_rsmp_process_dev(d, din, n, n, dout, Mo));
-  HIP_TRY(hipMemcpy2DAsync(out_host, (size_t)out_stride * es, dout, (size_t)Mo * es, (size_t)Mo * es, (size_t)d->nrows,
-                           hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return SDR_OK;
+  return run_staged(c, in_host, {rows, (size_t)n * es, (size_t)in_stride * es}, out_host, {rows, (size_t)Mo * es, (size_t)out_stride * es},
+                    [&](void* din, void* dout) { return sdr_rsmp_process_dev(d, (const float*)din, n, n, (float*)dout, Mo); });
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <list>
 #include <string>
 #include <vector>
@@ -96,6 +97,8 @@ int run_iir1(sdr_ctx* c, IirLaunch& a, const double* b, double a1, const char* w
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+constexpr double two_pi = 6.283185307179586476925286766559;
+
 }  // namespace sdrint
 
 #define HIP_TRY(expr)                                                                   \
@@ -113,3 +116,59 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 #define CHECK_CTX(c) \
   if ((c) == nullptr) return sdrint::fail(SDR_EINVAL, "context is NULL")
+
+// ---- what the row blocks' entry points share (ddc, pfb, rsmp, spectrum) ------------------------
+namespace sdrint {
+
+inline int taps_finite(const double* b, int taps, const char* what) {
+  for (int j = 0; j < taps; ++j)
+    if (!std::isfinite(b[j])) return fail(SDR_EINVAL, "%s: tap %d is not finite", what, j);
+  return SDR_OK;
+}
+
+// the call-time rules of a decimating block (an object with a decimation D), for host and device
+// buffers alike
+template <class Obj>
+int decim_check_call(const Obj* d, const void* iq, int64_t n, const float* out, int64_t out_stride, const char* what) {
+  if (d == nullptr) return fail(SDR_EINVAL, "%s: object is NULL", what);
+  if (iq == nullptr || out == nullptr) return fail(SDR_EINVAL, "%s: iq or out is NULL", what);
+  if (n < 1 || n % d->D != 0) return fail(SDR_EINVAL, "%s: n=%lld must be >= 1 and a multiple of decim=%d", what, (long long)n, d->D);
+  if (out_stride < n / d->D)
+    return fail(SDR_EINVAL, "%s: out_stride=%lld < n/decim=%lld", what, (long long)out_stride, (long long)(n / d->D));
+  return SDR_OK;
+}
+
+// a device copy of host[0..count), for a create's error chain (the host array is read until the
+// stream is synchronised)
+template <class T>
+hipError_t upload(T** dev, const T* host, size_t count, hipStream_t st) {
+  const hipError_t e = hipMalloc(dev, count * sizeof(T));
+  return e != hipSuccess ? e : hipMemcpyAsync(*dev, host, count * sizeof(T), hipMemcpyHostToDevice, st);
+}
+// how a create's error chain ends
+inline int create_failed(hipError_t e, const char* what) {
+  return fail(e == hipErrorOutOfMemory ? SDR_ENOMEM : SDR_EHIP, "%s: %s", what, hipGetErrorString(e));
+}
+
+// rows of row_bytes bytes each; on the host `pitch` bytes apart, packed on the device
+struct HostRows {
+  size_t rows, row_bytes, pitch;
+};
+// A synchronous host call of a block: the input rows to context slot S_IN, call(din, dout) -- the
+// block's process_dev on packed rows --, the output rows back from S_OUT, one wait.
+template <class F>
+int run_staged(sdr_ctx* c, const void* in_host, HostRows in, void* out_host, HostRows out, F&& call) {
+  void *din = nullptr, *dout = nullptr;
+  TRY(scratch(c, S_IN, in.rows * in.row_bytes, &din));
+  TRY(scratch(c, S_OUT, out.rows * out.row_bytes, &dout));
+  if (in.rows == 1)
+    HIP_TRY(hipMemcpyAsync(din, in_host, in.row_bytes, hipMemcpyHostToDevice, c->stream));
+  else
+    HIP_TRY(hipMemcpy2DAsync(din, in.row_bytes, in_host, in.pitch, in.row_bytes, in.rows, hipMemcpyHostToDevice, c->stream));
+  TRY(call(din, dout));
+  HIP_TRY(hipMemcpy2DAsync(out_host, out.pitch, dout, out.row_bytes, out.row_bytes, out.rows, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return SDR_OK;
+}
+
+}  // namespace sdrint

@@ -15,6 +15,7 @@ typedef _Float16 h2v __attribute__((ext_vector_type(2)));
 typedef float f4v __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+typedef uint32_t u2v __attribute__((ext_vector_type(2)));
 
 constexpr float MM_LO = 2048.f;                   // the lo parts' scale
 
@@ -31,6 +32,30 @@ static __device__ __forceinline__ void mm_split4(float4 x, h4v* hi, h4v* lo) {
   const h2v la = __builtin_convertvector(ra, h2v), lc = __builtin_convertvector(rc, h2v);
   *hi = h4v{ha.x, ha.y, hc.x, hc.y};
   *lo = h4v{la.x, la.y, lc.x, lc.y};
+}
+
+// The A operand of a GEMM whose rows are fixed at create time (ddc.hip, pfb.hip), pre-split in
+// fragment order.  A32: [16 NT][32 KS] f32 rows -> afrag [NT KS][hi, lo][64 lanes][8] (lane l of
+// step q = t KS + st: A[16 t + (l & 15)][32 st + 8 (l >> 4) + e]).  A template, so that only the
+// translation units that launch it emit it.
+template <typename T = float>
+__global__ void mm_prep_kernel(const T* A32, _Float16* afrag, int NT, int KS) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= NT * KS * 64) return;
+  const int q = i >> 6, l = i & 63, t = q / KS, st = q - t * KS;
+  const T* row = A32 + (size_t)(16 * t + (l & 15)) * (32 * KS) + 32 * st + 8 * (l >> 4);
+  _Float16* hi = afrag + ((size_t)q * 2 + 0) * 512 + 8 * l;
+  _Float16* lo = afrag + ((size_t)q * 2 + 1) * 512 + 8 * l;
+  for (int e = 0; e < 8; ++e) {
+    const MmHL p = mm_split(row[e]);
+    hi[e] = p.hi;
+    lo[e] = p.lo;
+  }
+}
+template <typename T>
+hipError_t mm_prep(const T* A32, _Float16* afrag, int NT, int KS, hipStream_t st) {
+  mm_prep_kernel<<<(NT * KS * 64 + 255) / 256, 256, 0, st>>>(A32, afrag, NT, KS);
+  return hipGetLastError();
 }
 
 // A buffer descriptor over bytes [p, p + bytes) from wave-uniform values (readfirstlane: the

@@ -410,7 +410,6 @@ int sdr_spec_create(sdr_ctx* c, int nfft, const double* window, int64_t hop, int
     return fail(SDR_EINVAL, "sdr_spec_create: hop=%lld outside [1, %d]", (long long)hop, SDR_SPEC_MAX_HOP);
   if (navg < 0) return fail(SDR_EINVAL, "sdr_spec_create: navg=%lld must be 0 (one row) or >= 1", (long long)navg);
   if (iq_dtype != SDR_IQ_F32 && iq_dtype != SDR_IQ_U8) return fail(SDR_EINVAL, "sdr_spec_create: bad iq_dtype %d", iq_dtype);
-  const double two_pi = 6.283185307179586476925286766559;
   std::vector<double> w(nfft);
   double wsum = 0.0;
   for (int i = 0; i < nfft; ++i) {
@@ -437,14 +436,12 @@ int sdr_spec_create(sdr_ctx* c, int nfft, const double* window, int64_t hop, int
     const double th = two_pi * (double)i / (double)nfft;
     tw[i] = float2{(float)std::cos(th), (float)-std::sin(th)};
   }
-  hipError_t e = hipMalloc(&d->win, w32.size() * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d->tw, tw.size() * sizeof(float2));
-  if (e == hipSuccess) e = hipMemcpyAsync(d->win, w32.data(), w32.size() * sizeof(float), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d->tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, c->stream);
+  hipError_t e = upload(&d->win, w32.data(), w32.size(), c->stream);
+  if (e == hipSuccess) e = upload(&d->tw, tw.data(), tw.size(), c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (the host vectors are read until here)
   if (e != hipSuccess) {
     sdr_spec_destroy(d);
-    return fail(e == hipErrorOutOfMemory ? SDR_ENOMEM : SDR_EHIP, "sdr_spec_create: %s", hipGetErrorString(e));
+    return create_failed(e, "sdr_spec_create");
   }
   *out = d;
   return SDR_OK;
@@ -521,17 +518,9 @@ int sdr_spec_run(sdr_spec* d, const void* iq_host, int64_t n, float* out_host, i
   TRY(set_dev(c));
   int64_t nseg, rows, navg;
   TRY(spec_geom(d, n, &nseg, &rows, &navg, "sdr_spec_run"));
-  const size_t es = d->dtype == SDR_IQ_U8 ? 1 : 4;
-  void* din = nullptr;
-  float* dout = nullptr;
-  TRY(scratch(c, S_IN, (size_t)2 * n * es, &din));
-  TRY(scratch(c, S_OUT, (size_t)rows * d->N * sizeof(float), (void**)&dout));
-  HIP_TRY(hipMemcpyAsync(din, iq_host, (size_t)2 * n * es, hipMemcpyHostToDevice, c->stream));
-  TRY(sdr_spec_process_dev(d, din, n, dout, d->N));
-  HIP_TRY(hipMemcpy2DAsync(out_host, (size_t)out_stride * 4, dout, (size_t)d->N * 4, (size_t)d->N * 4, (size_t)rows,
-                           hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return SDR_OK;
+  const size_t es = d->dtype == SDR_IQ_U8 ? 2 : 8, N = (size_t)d->N;
+  return run_staged(c, iq_host, {1, (size_t)n * es, 0}, out_host, {(size_t)rows, N * 4, (size_t)out_stride * 4},
+                    [&](void* din, void* dout) { return sdr_spec_process_dev(d, din, n, (float*)dout, d->N); });
 }
 
 }  // extern "C"

@@ -11,41 +11,15 @@ from the build's ddc.res.  One JSON line.
                            [--res real-time-software-defined-radio_amd/_build/ddc.res]
 """
 import argparse
-import ctypes
 import json
-import os
-import re
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import rtsdr  # noqa: E402
+import _blocktime as bt
+from _blocktime import rtsdr
 
 HBM_PEAK_GBS = 8000.0
 CUS, SIMDS, CLOCK_GHZ, MFMA_CYCLES = 256, 4, 2.4, 16      # v_mfma_f32_16x16x32_f16 back to back: ~16 cycles per SIMD
-
-
-def kernel_resources(path):
-    """{kernel: {VGPRs, AGPRs, LDS, Occupancy, Scratch}} of the ddc kernels from the build's remarks"""
-    out, cur = {}, None
-    if not os.path.exists(path):
-        return out
-    keys = {"VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy",
-            "LDS Size [bytes/block]": "static_lds"}
-    for line in open(path, errors="replace"):
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            m2 = re.search(r"ddc_mma_kernelILi(\d+)ELb(\d)ELb(\d)", name)
-            cur = out.setdefault(f"ddc_mma_kernel<CB={m2.group(1)},{'u8' if m2.group(2) == '1' else 'f32'},"
-                                 f"{'A in LDS' if m2.group(3) == '1' else 'A from L2'}>", {}) if m2 else None
-            continue
-        m = re.search(r"remark:\s+([A-Za-z \[\]/]+): (\S+)", line)
-        if m and cur is not None and m.group(1).strip() in keys:
-            cur[keys[m.group(1).strip()]] = int(m.group(2))
-    return out
 
 
 def main():
@@ -56,7 +30,7 @@ def main():
     ap.add_argument("--log2n", type=int, default=25)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--res", default=os.path.join(ROOT, "real-time-software-defined-radio_amd", "_build", "ddc.res"),
+    ap.add_argument("--res", default=bt.res_path("ddc"),
                     help="the build's resource remarks of csrc/ddc.hip")
     a = ap.parse_args()
     ctx = rtsdr.get_context()
@@ -76,20 +50,7 @@ def main():
         din = rtsdr.DeviceBuffer.from_array(ctx, iq)
         del iq
         ch = rtsdr.Channelizer(freqs, 1.0, D, taps=T, iq_dtype=dt, ctx=ctx)
-        tm = rtsdr.Timer(ctx)
-        for _ in range(a.warmup):
-            ch.process_dev(din.ptr, n, out.ptr, stride)
-        ctx.synchronize()
-        ms = []
-        for _ in range(a.reps):
-            e0, e1 = tm.event(), tm.event()
-            tm.record(e0)
-            ch.process_dev(din.ptr, n, out.ptr, stride)
-            tm.record(e1)
-            ctx.synchronize()
-            ms.append(tm.elapsed_ms(e0, e1))
-        tm.close()
-        ms = np.array(ms)
+        (ms,) = bt.event_ms(ctx, [lambda: ch.process_dev(din.ptr, n, out.ptr, stride)], a.reps, a.warmup)
         nbytes = 2 * n * np.dtype(dt).itemsize + C * 8 * M
         mfmas = (M / 16) * NT * KS * (3 if dt == np.float32 else 2)
         res[name] = {"best_us": round(float(ms.min()) * 1e3, 1), "median_us": round(float(np.median(ms)) * 1e3, 1),
@@ -100,12 +61,12 @@ def main():
                      "mfma_pipe_us": round(mfmas * MFMA_CYCLES / (CUS * SIMDS * CLOCK_GHZ * 1e3), 1)}
         ch.close()
         din.free()
-    gbs = ctypes.c_double(0.0)
-    rtsdr._lib.check(ctx.lib.sdr_copy_bandwidth(ctx.handle, 256 << 20, 20, ctypes.byref(gbs)), "sdr_copy_bandwidth")
-    res["copy_gbs"] = round(gbs.value, 1)
+    gbs = bt.copy_gbs(ctx)
+    res["copy_gbs"] = round(gbs, 1)
     for name in ("f32", "u8"):
-        res[name]["share_of_copy_best"] = round(res[name]["gbs_best"] / gbs.value, 4)
-    res["kernels"] = kernel_resources(a.res)
+        res[name]["share_of_copy_best"] = round(res[name]["gbs_best"] / gbs, 4)
+    res["kernels"] = bt.kernel_resources(a.res, r"ddc_mma_kernelILi(\d+)ELb(\d)ELb(\d)", bt.mma_label("ddc_mma_kernel"),
+                                         ("vgprs", "agprs", "scratch", "occupancy", "static_lds"))
     print(json.dumps(res))
 
 

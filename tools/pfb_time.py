@@ -18,39 +18,15 @@ the kernels' register / occupancy remarks from the build's pfb.res.  One JSON li
                            [--res real-time-software-defined-radio_amd/_build/pfb.res]
 """
 import argparse
-import ctypes
 import json
-import os
-import re
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import rtsdr  # noqa: E402
+import _blocktime as bt
+from _blocktime import rtsdr
 
 HBM_PEAK_GBS = 8000.0
 CUS, SIMDS, CLOCK_GHZ, MFMA_CYCLES = 256, 4, 2.4, 16      # v_mfma_f32_16x16x32_f16 back to back: ~16 cycles per SIMD
-
-
-def kernel_resources(path):
-    """{kernel: {vgprs, agprs, occupancy, scratch}} of the pfb kernels from the build's remarks"""
-    out, cur = {}, None
-    if not os.path.exists(path):
-        return out
-    keys = {"VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy"}
-    for line in open(path, errors="replace"):
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            m2 = re.search(r"pfb_mma_kernelILi(\d+)ELb(\d)ELb(\d)", m.group(1))
-            cur = out.setdefault(f"pfb_mma_kernel<CB={m2.group(1)},{'u8' if m2.group(2) == '1' else 'f32'},"
-                                 f"{'A in LDS' if m2.group(3) == '1' else 'A from L2'}>", {}) if m2 else None
-            continue
-        m = re.search(r"remark:\s+([A-Za-z \[\]/]+): (\S+)", line)
-        if m and cur is not None and m.group(1).strip() in keys:
-            cur[keys[m.group(1).strip()]] = int(m.group(2))
-    return out
 
 
 def make_input(ctx, n, dt):
@@ -61,22 +37,7 @@ def make_input(ctx, n, dt):
 
 def time_objects(ctx, objs, din, n, out, stride, reps, warmup):
     """the objects' calls interleaved: [ms per repeat] per object"""
-    tm = rtsdr.Timer(ctx)
-    for _ in range(warmup):
-        for o in objs:
-            o.process_dev(din.ptr, n, out.ptr, stride)
-    ctx.synchronize()
-    ms = [[] for _ in objs]
-    for _ in range(reps):
-        for i, o in enumerate(objs):
-            e0, e1 = tm.event(), tm.event()
-            tm.record(e0)
-            o.process_dev(din.ptr, n, out.ptr, stride)
-            tm.record(e1)
-            ctx.synchronize()
-            ms[i].append(tm.elapsed_ms(e0, e1))
-    tm.close()
-    return [np.array(v) for v in ms]
+    return bt.event_ms(ctx, [lambda o=o: o.process_dev(din.ptr, n, out.ptr, stride) for o in objs], reps, warmup)
 
 
 def report(ms, n, D, nch, itemsize, mfmas):
@@ -95,7 +56,7 @@ def main():
     ap.add_argument("--log2n-fm", type=int, default=24)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--res", default=os.path.join(ROOT, "real-time-software-defined-radio_amd", "_build", "pfb.res"),
+    ap.add_argument("--res", default=bt.res_path("pfb"),
                     help="the build's resource remarks of csrc/pfb.hip")
     a = ap.parse_args()
     ctx = rtsdr.get_context()
@@ -136,12 +97,12 @@ def main():
         din.free()
     out.free()
 
-    gbs = ctypes.c_double(0.0)
-    rtsdr._lib.check(ctx.lib.sdr_copy_bandwidth(ctx.handle, 256 << 20, 20, ctypes.byref(gbs)), "sdr_copy_bandwidth")
-    res["copy_gbs"] = round(gbs.value, 1)
+    gbs = bt.copy_gbs(ctx)
+    res["copy_gbs"] = round(gbs, 1)
     for r in (res["shared"]["pfb"], res["shared"]["ddc"], res["fm_band"]["f32"], res["fm_band"]["u8"]):
-        r["share_of_copy_best"] = round(r["gbs_best"] / gbs.value, 4)
-    res["kernels"] = kernel_resources(a.res)
+        r["share_of_copy_best"] = round(r["gbs_best"] / gbs, 4)
+    res["kernels"] = bt.kernel_resources(a.res, r"pfb_mma_kernelILi(\d+)ELb(\d)ELb(\d)", bt.mma_label("pfb_mma_kernel"),
+                                         ("vgprs", "agprs", "scratch", "occupancy"))
     print(json.dumps(res))
 
 

@@ -19,14 +19,12 @@ the timed rows are compared with the host layer's before anything is timed.  One
 import argparse
 import json
 import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import rtsdr  # noqa: E402
+import _blocktime as bt
+from _blocktime import rtsdr
 
 N = 256 * 3648                     # a C5 span's rrc_i row: 256 blocks of 3648 samples
 
@@ -45,24 +43,7 @@ def make_rows(S, n, sigma):
 
 
 def event_times(ctx, call, reps, warmup, before=None):
-    tm = rtsdr.Timer(ctx)
-    for _ in range(warmup):
-        if before:
-            before()
-        call()
-    ctx.synchronize()
-    ms = []
-    for _ in range(reps):
-        if before:
-            before()
-        e0, e1 = tm.event(), tm.event()
-        tm.record(e0)
-        call()
-        tm.record(e1)
-        ctx.synchronize()
-        ms.append(tm.elapsed_ms(e0, e1))
-    tm.close()
-    ms = np.array(ms)
+    (ms,) = bt.event_ms(ctx, [call], reps, warmup, before)
     return {"best_us": round(float(ms.min()) * 1e3, 1), "median_us": round(float(np.median(ms)) * 1e3, 1)}
 
 

@@ -21,54 +21,15 @@ JSON line.
 import argparse
 import ctypes
 import json
-import os
-import re
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import rtsdr  # noqa: E402
+import _blocktime as bt
+from _blocktime import rtsdr
 
 HBM_PEAK_GBS = 8000.0
 SHAPES = ((1024, 1024), (4096, 4096), (8192, 8192), (4096, 2048))      # (nfft, hop)
 NAVGS = (0, 64)
-
-
-def kernel_resources(path):
-    """{kernel: {vgprs, agprs, occupancy, scratch, lds}} of the spectrum kernels from the build's remarks"""
-    out, cur = {}, None
-    if not os.path.exists(path):
-        return out
-    keys = {"VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy"}
-    for line in open(path, errors="replace"):
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            m2 = re.search(r"spec_kernelILi(\d+)ELb(\d)", m.group(1))
-            cur = out.setdefault(f"spec_kernel<nfft={1 << int(m2.group(1))},{'u8' if m2.group(2) == '1' else 'f32'}>", {}) if m2 else None
-            continue
-        m = re.search(r"remark:\s+([A-Za-z \[\]/]+): (\S+)", line)
-        if m and cur is not None and m.group(1).strip() in keys:
-            cur[keys[m.group(1).strip()]] = int(m.group(2))
-    return out
-
-
-def time_spec(ctx, sp, din, n, out, reps, warmup):
-    tm = rtsdr.Timer(ctx)
-    for _ in range(warmup):
-        sp.process_dev(din.ptr, n, out.ptr)
-    ctx.synchronize()
-    ms = []
-    for _ in range(reps):
-        e0, e1 = tm.event(), tm.event()
-        tm.record(e0)
-        sp.process_dev(din.ptr, n, out.ptr)
-        tm.record(e1)
-        ctx.synchronize()
-        ms.append(tm.elapsed_ms(e0, e1))
-    tm.close()
-    return np.array(ms)
 
 
 def torch_form(torch, t, u8, w, nfft, hop, nseg, rows, navg):
@@ -100,7 +61,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-torch", action="store_true")
-    ap.add_argument("--res", default=os.path.join(ROOT, "real-time-software-defined-radio_amd", "_build", "spectrum.res"),
+    ap.add_argument("--res", default=bt.res_path("spectrum"),
                     help="the build's resource remarks of csrc/spectrum.hip")
     a = ap.parse_args()
     ctx = rtsdr.get_context()
@@ -130,7 +91,7 @@ def main():
             for navg in NAVGS:
                 sp = rtsdr.Spectrum(nfft, 19.2e6, hop=hop, navg=navg, iq_dtype=dt, ctx=ctx)
                 nseg, rows = sp.rows(n)
-                ms = time_spec(ctx, sp, din, n, out, a.reps, a.warmup)
+                (ms,) = bt.event_ms(ctx, [lambda: sp.process_dev(din.ptr, n, out.ptr)], a.reps, a.warmup)
                 nbytes = iq.nbytes + rows * nfft * 4
                 if nbytes not in read_gbs:
                     g = ctypes.c_double(0.0)
@@ -160,7 +121,9 @@ def main():
         din.free()
         del t
     out.free()
-    res["kernels"] = kernel_resources(a.res)
+    res["kernels"] = bt.kernel_resources(a.res, r"spec_kernelILi(\d+)ELb(\d)",
+                                         lambda m: f"spec_kernel<nfft={1 << int(m.group(1))},{'u8' if m.group(2) == '1' else 'f32'}>",
+                                         ("vgprs", "agprs", "scratch", "occupancy"))
     print(json.dumps(res))
 
 
