@@ -27,7 +27,7 @@ RX_OUTPUTS = ("demod", "audio", "bpf_recovery", "nco", "bpf_extraction", "stereo
               "extract", "pre_pll", "nco_i", "nco_q", "lpf_i", "lpf_q", "resample_i", "resample_q",
               "rrc_i", "rrc_q", "audio_de", "left_de", "right_de")
 # stage C: the stereo mixer + LPF (and the RDS LPF rows when kept); "resample": the RDS mixers +
-# LPF + x19/80 resampler (the composite filter, csrc/rx.hip rx_cres_kernel)
+# LPF + x19/80 resampler (the composite filter, csrc/rx_stage.hip rx_cres_kernel)
 RX_STAGES = ("fe", "filters_of_demod", "rds_square", "pll", "mix_lpf", "resample", "rrc")
 # PLL solve counters (include/sdr.h SDR_PLL_ST_*)
 # device-side RDS link layer (include/sdr.h sdr_rds_links_*)

@@ -224,6 +224,8 @@ class Receiver(_Handle):
         return [n for k, n in enumerate(RX_OUTPUTS) if self._produces(k)]
 
     def _produces(self, k):
+        # mirrors the `group` and `deemph` columns of kOutput (csrc/rx_layout.h), which the library
+        # answers from only once the receiver is finalised; tests/test_receiver.py holds the two together
         name = RX_OUTPUTS[k]
         if name == "demod":
             return True

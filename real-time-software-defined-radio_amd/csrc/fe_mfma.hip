@@ -199,7 +199,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SDR_FE_MFMA_
 #pragma unroll
     for (int dg = 0; dg < 3; ++dg) asm volatile("" : : "v"(afr[ks][dg]));
   // audio taps reversed (g[j] = h[150 - j]), tap pairs as SGPR operands (scalar loads at
-  // compile-time offsets, as rx.hip's fir_tile)
+  // compile-time offsets, as rx_stage.hip's fir_tile)
   const cfp4 gr = (cfp4)p.argev;
 
   // ---- tile images: chunk c = lane + 64 q (16 raw bytes = 8 complex u8 samples) ----

@@ -1,5 +1,6 @@
 // Host-side internals of a libsdr context, shared by the C-ABI translation units
-// (capi.hip: the per-call entry points; rx.hip: the multi-stream block receiver).
+// (capi.hip: the per-call entry points; rx.hip: the multi-stream block receiver, whose stage
+// kernels are rx_stage.hip and do not see a context).
 // Not part of the public ABI (include/sdr.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -116,6 +117,8 @@ constexpr double two_pi = 6.283185307179586476925286766559;
 
 #define CHECK_CTX(c) \
   if ((c) == nullptr) return sdrint::fail(SDR_EINVAL, "context is NULL")
+#define CHECK_RX(r) \
+  if ((r) == nullptr) return sdrint::fail(SDR_EINVAL, "sdr_rx is NULL")
 
 // ---- what the row blocks' entry points share (ddc, pfb, rsmp, spectrum) ------------------------
 namespace sdrint {

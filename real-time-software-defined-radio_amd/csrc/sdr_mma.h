@@ -1,4 +1,4 @@
-// f32 accuracy from f16 matrix-core operands, shared by the MFMA kernels (rx.hip: the D = 1
+// f32 accuracy from f16 matrix-core operands, shared by the MFMA kernels (rx_stage.hip: the D = 1
 // FIRs; ddc.hip: the channelizer): every operand is split as v = hi + lo / 2048
 // (hi = f16(v), lo = f16((v - hi) 2048): 22 significant bits) and a product is
 //   sum(a_hi b_hi) + (sum(a_hi b_lo) + sum(a_lo b_hi)) / 2048

@@ -1,6 +1,6 @@
 // The NCO of fmPll (model/fmPll.py:33-37) as a function of the PLL's stored phase rows, shared
 // by the PLL kernels (pll.hip: NCO rows, when an output asks for them) and the receiver's mixer
-// stage (rx.hip: the mixers form cos / sin of the PLL phase where they stage their inputs, so a
+// stage (rx_stage.hip: the mixers form cos / sin of the PLL phase where they stage their inputs, so a
 // block's NCO never round-trips through HBM -- VERDICT r04 item 2).
 //
 //   th_k   = 2 pi (freq / Fs) (trigOffset + k + 1) + phaseEst_k        (fmPll.py:33)
@@ -199,7 +199,7 @@ __device__ __forceinline__ void nco_value(double w, double scale, double adj, in
   sdrnco::sincos_red<OPAQUE>(sdrnco::reduce_2pi(a), sv, cv);
 }
 
-// ---- the mixers' NCO (rx.hip): f32 cos / sin of the f64 angle ------------------------------
+// ---- the mixers' NCO (rx_stage.hip): f32 cos / sin of the f64 angle ------------------------------
 // The mixers only need the NCO to the f32 rounding of their product: the angle a = th scale +
 // adj is formed and reduced in f64 exactly as above (|y| <= pi/4 after the quadrant), then
 // y is rounded to f32 (3e-8) and cos / sin come from f32 polynomials on two samples at once
@@ -353,7 +353,7 @@ __device__ __forceinline__ void nco_f32x4(const NcoSrc& N, const NcoTile& T, int
 }
 
 // The matrix-core mixers' loads of inputs i .. i+3 (i >= 1 odd), issued ahead of their use
-// (software-pipelined, rx.hip): the phase pairs and, when the tile's pseudo-blocks carry a
+// (software-pipelined, rx_stage.hip): the phase pairs and, when the tile's pseudo-blocks carry a
 // linear response (lin: uniform), the response rows (f32, r06).
 struct Nco4Ld {
   typedef double d2n __attribute__((ext_vector_type(2)));
@@ -396,7 +396,7 @@ __device__ __forceinline__ void nco4_load(const NcoSrc& N, const NcoTile& T, int
   }
 }
 
-// The matrix-core mixers' angle, per window (rx.hip rx_stereomm_kernel / rx_cresmm_kernel):
+// The matrix-core mixers' angle, per window (rx_stage.hip rx_decmm_kernel / rx_cresmm_kernel):
 // a_k = ws (off + k) + (phaseEst_{k-1}) scale + adj with phaseEst = stored + 2 pi shift (+ the
 // linear response) is formed as
 //   a_k = base_h + ws (k - kw) + stored scale (+ scale (rr . d)),

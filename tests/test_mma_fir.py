@@ -1,4 +1,4 @@
-"""The matrix-core FIR's arithmetic (csrc/rx.hip rx_mma_kernel): f16 hi/lo operand splits
+"""The matrix-core FIR's arithmetic (csrc/rx_stage.hip rx_mma_kernel): f16 hi/lo operand splits
 (v = hi + lo / 2048), three f16 products per tap accumulated in f32, the lo x lo product
 dropped.  A numpy emulation of that arithmetic against f64 lfilter, next to the f32 direct
 form the VALU tiles compute: the split form must be as accurate (the receiver's parity

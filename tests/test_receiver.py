@@ -1,4 +1,5 @@
-"""The multi-stream block receiver (sdr_rx_*, csrc/rx.hip) on the GPU: SURVEY §8a C5 --
+"""The multi-stream block receiver (sdr_rx_*, csrc/rx.hip; its stage kernels, csrc/rx_stage.hip)
+on the GPU: SURVEY §8a C5 --
 8 independent u8 streams (seeds 0-7, B = 153 600 complex, src/fm_radio.cpp:23) through
 mono + stereo + RDS to the RRC output at once -- against the CPU oracle's restatement of
 model/fmMonoBlock.py:80-173 and model/fmRDSblock.py:127-204, with every state carried across
@@ -252,3 +253,27 @@ def test_receiver_set_pll_between_blocks(sdr, gpu_ctx, oracle):
     assert err < NCO_TOL
     assert off > NCO_TOL                       # (the input tells the two loops apart)
     assert maxabs(rx.state()[1][0], st_want) < 1e-6
+
+
+@pytest.mark.parametrize("de", [None, 75e-6])
+def test_receiver_outputs_match_the_library(sdr, gpu_ctx, de):
+    """Receiver.outputs (blocks.py's _produces, answered before the library object is finalised) names
+    exactly the outputs sdr_rx_output accepts (kOutput, csrc/rx_layout.h), for every flag combination,
+    with de-emphasis wherever the flags produce audio.  The smallest block; no IQ is processed."""
+    from importlib import import_module
+    names = import_module("real-time-software-defined-radio_amd._lib").RX_OUTPUTS
+    for mono in (False, True):
+        for stereo in (False, True):
+            for rds in (False, True):
+                rx = sdr.Receiver(1, 1, mono=mono, stereo=stereo, rds=rds, deemphasis=de if mono or stereo else None)
+                try:
+                    accepted = []
+                    for name in names:
+                        try:
+                            rx.output_ptr(name)
+                            accepted.append(name)
+                        except ValueError as e:            # only the library's "not produced" answer counts
+                            assert "is not produced by flags" in str(e), (name, str(e))
+                    assert rx.outputs == accepted, (mono, stereo, rds, de)
+                finally:
+                    rx.close()

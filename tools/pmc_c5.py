@@ -11,7 +11,7 @@ MI355X_MICROARCH.md), WRITE_SIZE, SQ_INSTS_VALU_MFMA_MOPS_F16 / _I8 (x 512 = exe
 matrix-core ops), SQ_INSTS_VALU_{FMA,ADD,MUL,TRANS}_F64, SQ_INSTS_VALU, SQ_WAVES,
 SQ_ACTIVE_INST_VALU (quad-cycles of vector issue), SQ_VALU_MFMA_BUSY_CYCLES (matrix-pipe cycles).
 
-The stages are the receiver's timing stages (csrc/rx.hip, sdr_rx_stage_ms):
+The stages are the receiver's timing stages (csrc/rx.hip, sdr_rx_stage_ms; the rx_* kernels: csrc/rx_stage.hip):
   fe                fe_mfma_demod_kernel<151>
   filters_of_demod  rx_mma_kernel<151, 3> (pilot, stereo, RDS-extract BPFs) + rx_decmm_kernel<false, false> (audio LPF)
   rds_square        the first rx_mma_kernel<151, 1> dispatch of a span call (x^2 + BPF)

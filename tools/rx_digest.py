@@ -1,7 +1,8 @@
 """Digest of the receiver's outputs (GPU box): for a fixed list of receiver configurations, 3
-consecutive calls each, a SHA-256 (its first 16 hex digits) of every row the receiver reports as
-made and of state(); then
-sdr_pll_dev at a spec-only and a long length.  Two libraries compute the same thing when their
+consecutive calls each, where its output rows lie (each produced output's byte offset from the first
+one's pointer, its stride and its n, as sdr_rx_output reports them), a SHA-256 (its first 16 hex
+digits) of every row the receiver reports as made and of state(); then sdr_pll_dev at a spec-only
+and a long length.  Two libraries compute the same thing when their
 outputs are identical line for line (tools/build_dbg.sh builds another libsdr, SDR_LIB selects it):
   python tools/rx_digest.py > new.txt; SDR_LIB=.../libsdr_parent.so python tools/rx_digest.py > parent.txt
 usage: python tools/rx_digest.py"""
@@ -20,16 +21,26 @@ _lib = import_module("real-time-software-defined-radio_amd._lib")
 B5, CALLS = 153_600, 3
 ALL = dict(stereo=True, rds=True)
 LEAN = ("nco", "nco_i", "nco_q", "lpf_i", "lpf_q", "bpf_recovery", "pre_pll")   # tests/test_span.py's lean keep list
-# name, streams, blocks per call, IQ dtype, Receiver arguments
+DE = dict(deemphasis=75e-6)
+# name, streams, blocks per call, IQ dtype, Receiver arguments (and lean: the lean keep list; extra:
+# samples beyond the whole blocks; submit: also the submit path, from a reset; fetch: what it asks for)
 CONFIGS = [
     ("block_f32", 2, 1, np.float32, dict(ALL)),
     ("block_u8", 2, 1, np.uint8, dict(ALL)),
-    ("block_pipe_depth2", 2, 1, np.uint8, dict(ALL, pipeline=True, depth=2)),
+    ("block_pipe_depth2", 2, 1, np.uint8, dict(ALL, pipeline=True, depth=2, submit=True)),
     ("block_rf51", 2, 1, np.float32, dict(ALL, rf_coeff=sdr.design.mono_coeffs(51, 151)[0])),
     ("span4_full", 3, 4, np.uint8, dict(ALL)),
     ("span4_lean", 3, 4, np.uint8, dict(ALL, lean=True)),
     ("span4_deemph", 2, 4, np.uint8, dict(ALL, deemphasis=75e-6)),
     ("mono_only", 2, 1, np.uint8, dict()),
+    ("mono_deemph", 2, 1, np.uint8, dict(DE)),
+    ("stereo_deemph", 2, 1, np.uint8, dict(DE, stereo=True)),              # audio_de kept: the de_mono branch
+    ("rds_only", 2, 1, np.uint8, dict(mono=False, rds=True)),
+    ("span4_valu", 1, 4, np.uint8, dict(ALL, extra=10)),                   # M = 61 441, no multiple of 4: the VALU tiles
+    ("block_pipe_depth1", 2, 1, np.uint8, dict(ALL, pipeline=True, submit=True)),
+    ("block_pipe_depth3", 2, 1, np.uint8, dict(ALL, pipeline=True, depth=3, submit=True)),
+    ("block_submit_copy", 2, 1, np.uint8,                                  # demod and nco come back by copy
+     dict(ALL, pipeline=True, depth=2, submit=True, fetch=("demod", "nco", "audio", "left", "rrc_i"))),
 ]
 
 
@@ -39,13 +50,15 @@ def sha(a):
 
 def receiver(tag, S, K, dt, kw):
     kw = dict(kw)
-    n = K * B5
+    lean, submit, fetch = kw.pop("lean", False), kw.pop("submit", False), kw.pop("fetch", None)
+    n = K * B5 + kw.pop("extra", 0)
     iq = np.stack([sdr.synth.fm_iq(CALLS * n, seed=200 + s, dtype=dt) for s in range(S)])
     ctx = sdr.get_context()
     d = _lib.DeviceBuffer.from_array(ctx, iq)
     ctx.synchronize()
-    lean = kw.pop("lean", False)
     rx = sdr.Receiver(S, n, iq_dtype=dt, **kw)
+    ptrs = {name: rx.output_ptr(name) for name in rx.outputs}
+    print(f"{tag} layout " + " ".join(f"{name}:{p - ptrs['demod'][0]}:{st}:{m}" for name, (p, st, m) in ptrs.items()))
     if lean:
         rx.set_keep([nm for nm in rx.outputs if nm not in LEAN])
     for k in range(CALLS):
@@ -59,9 +72,9 @@ def receiver(tag, S, K, dt, kw):
                 print(f"{tag} call {k} {name} -")
         if kw.get("deemphasis"):
             print(f"{tag} call {k} pcm {sha(rx.pcm())}")
-    if kw.get("depth", 1) > 1:                             # and the submit path, from a reset
+    if submit:                                             # and the submit path, from a reset
         rx.reset()
-        outs = [rx.submit(iq[:, 2 * k * n:2 * (k + 1) * n]) for k in range(CALLS)]
+        outs = [rx.submit(iq[:, 2 * k * n:2 * (k + 1) * n], fetch) for k in range(CALLS)]
         for k, o in enumerate([o for o in outs if o is not None] + rx.flush()):
             for name in sorted(o):
                 print(f"{tag} submit {k} {name} {sha(o[name])}")
