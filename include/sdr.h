@@ -533,6 +533,45 @@ int  sdr_spec_rows(sdr_spec* spec, int64_t n, int64_t* nseg, int64_t* rows);    
 int  sdr_spec_process_dev(sdr_spec* spec, const void* iq, int64_t n, float* out, int64_t out_stride); /* async */
 int  sdr_spec_run(sdr_spec* spec, const void* iq_host, int64_t n, float* out_host, int64_t out_stride); /* sync */
 
+/* ---- spectrum of rows of real samples (a receiver's demodulated rows) ----------------------
+ * The same Welch periodogram for `nrows` rows of real f32 samples in device memory, one-sided, in
+ * one call -- a receiver's "demod" rows (the FM multiplex at 240 kS/s), read in place: does a
+ * stream hold a 19 kHz pilot, an RDS subcarrier?  Row q starts q in_stride floats into x.  With
+ * segment s of row q starting at sample s hop, N = nfft and the window w,
+ *   X_{q,s}[k]   = sum_{i < N} w[i] x_q[s hop + i] exp(-2 pi i k i / N),        k = 0 .. N / 2
+ *   out[q][r][k] = (c_k / (navg (sum w)^2)) sum_{s in [r navg, (r + 1) navg)} |X_{q,s}[k]|^2,
+ *   c_0 = c_{N/2} = 1, otherwise 2
+ * linear power in f32, bin k centred on k fs / N.  For hop <= nfft this is
+ * scipy.signal.spectrogram(x_q, window=w, nperseg=N, noverlap=N-hop, detrend=False,
+ * return_onesided=True, scaling='spectrum', mode='psd') averaged over groups of navg columns.
+ * nseg, navg = 0, rows, trailing segments, nfft, hop and window: as sdr_spec's, per row.
+ * nrows: 1 .. SDR_RSPEC_MAX_ROWS.  Stateless.
+ * The sdr_spec transform with two real segments of one row per complex transform (segment a the
+ * real part, b the imaginary part: |A[k]|^2 + |B[k]|^2 = (|Z[k]|^2 + |Z[N-k]|^2) / 2, folded at
+ * the final store); a pair lies inside one chunk of one output row, an odd count pairs the last
+ * segment with zeros.  One launch over all rows, output rows and chunks, plus sdr_spec's second
+ * launch where an output row is summed in chunks; the chunk rule counts the segments of all
+ * nrows rows.  No atomics: the same call gives the same bits.  A non-finite sample makes every
+ * bin of its output row NaN, and no other row.
+ * sdr_rspec_rows: host arithmetic only; nseg and rows per input row.  sdr_rspec_process_dev:
+ * async; x and out aligned to 4 B (rows at any 4-byte alignment; the in_stride - n floats between
+ * rows are never read); output row (q, r) starts (q rows + r) out_stride floats into out and
+ * holds nfft / 2 + 1 floats, the rest of the stride is not written.  All sample offsets are
+ * 64-bit.  sdr_rspec_run: host rows in_stride floats apart, host output rows out_stride apart.
+ * SDR_EINVAL (before any device work): nrows, nfft, hop or navg out of range, a non-finite window
+ * value, a window that sums to zero, NULL pointers, n < nfft, an n that yields no complete row,
+ * in_stride < n, out_stride < nfft / 2 + 1, a misaligned pointer.  No host fallback. */
+#define SDR_RSPEC_MAX_ROWS 65535
+typedef struct sdr_rspec sdr_rspec;
+int  sdr_rspec_create(sdr_ctx* ctx, int nrows, int nfft, const double* window /* [nfft]; NULL = periodic Hann */,
+                      int64_t hop, int64_t navg, sdr_rspec** out);
+void sdr_rspec_destroy(sdr_rspec* rspec);
+int  sdr_rspec_rows(sdr_rspec* rspec, int64_t n, int64_t* nseg, int64_t* rows);   /* host arithmetic only */
+int  sdr_rspec_process_dev(sdr_rspec* rspec, const float* x, int64_t n, int64_t in_stride,
+                           float* out, int64_t out_stride);                      /* async */
+int  sdr_rspec_run(sdr_rspec* rspec, const float* x_host, int64_t n, int64_t in_stride,
+                   float* out_host, int64_t out_stride);                         /* sync */
+
 /* ---- spectral diagnostics -----------------------------------------
  * Bartlett PSD, model/fmSupportLib.py:66-140 (estimatePSD; the C++ src/fourier.cpp:36-110
  * advances sample and list positions by the same nfft/2 and is not the parity target):

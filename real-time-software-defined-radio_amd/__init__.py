@@ -17,15 +17,18 @@ frequencies) and FilterBank (a uniform grid of bins: the filter's work shared by
 and RowResampler between them and the Receiver where fs / decim is not its 2.4 MS/s;
 the RDS link layer behind the receiver's RRC rows: RdsLinkLayer (host, one stream) and
 RdsLinkBank (device, every stream of a call), rds_groups; the capture's spectrum / waterfall and the
-station finder in front of them: Spectrum (device), find_channels (host).
+station finder in front of them: Spectrum (device), find_channels (host); the spectrum of every
+stream's demodulated row and the stereo / RDS indicators behind the receiver: RowSpectrum (device,
+Receiver.mpx_spectrum), mpx_quality (host).
 See DESIGN.md and INTEGRATION.md.
 """
 from . import design, synth  # noqa: F401
 from ._lib import (SDR_IQ_F32, SDR_IQ_U8, SDR_PRE_MIX, SDR_PRE_NONE, SDR_PRE_SQUARE, Context,  # noqa: F401
                    DeviceBuffer, SdrError, SdrUnavailable, Timer, device_count, device_info, get_context,
                    load_library)
-from .blocks import (Channelizer, FilterBank, MonoBlockProcessor, RdsBlockProcessor, RdsLinkBank, RdsLinkLayer,  # noqa: F401
-                     Receiver, RowResampler, Spectrum, StereoBlockProcessor, find_channels, rds_groups, spectrum_rows)
+from .blocks import (Channelizer, FilterBank, MonoBlockProcessor, MpxQuality, RdsBlockProcessor, RdsLinkBank, RdsLinkLayer,  # noqa: F401
+                     Receiver, RowResampler, RowSpectrum, Spectrum, StereoBlockProcessor, find_channels, mpx_quality, rds_groups,
+                     spectrum_rows)
 from .design import impulseResponseRootRaisedCosine, my_filterImpulseResponse  # noqa: F401
 from .dsp import (DFT, MonoState, estimatePSD, fm_mono_range, fm_mono_streams, split_halo, fmDemodArctan, fmPll, lfilter, lfilter_decim,  # noqa: F401
                   audio_out, deemphasis, iir1, mono_block, my_convoloution, resample, rf_frontend_block)

@@ -143,6 +143,11 @@ SIGNATURES = {
     "sdr_spec_rows": (_i32, [_vp, _i64, _c.POINTER(_i64), _c.POINTER(_i64)]),
     "sdr_spec_process_dev": (_i32, [_vp, _vp, _i64, _vp, _i64]),
     "sdr_spec_run": (_i32, [_vp, _vp, _i64, _vp, _i64]),
+    "sdr_rspec_create": (_i32, [_vp, _i32, _i32, _dp, _i64, _i64, _c.POINTER(_vp)]),
+    "sdr_rspec_destroy": (None, [_vp]),
+    "sdr_rspec_rows": (_i32, [_vp, _i64, _c.POINTER(_i64), _c.POINTER(_i64)]),
+    "sdr_rspec_process_dev": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64]),
+    "sdr_rspec_run": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64]),
     "sdr_rds_link_create": (_i32, [_c.POINTER(_vp)]),
     "sdr_rds_link_destroy": (None, [_vp]),
     "sdr_rds_link_set_resync": (_i32, [_vp, _i32]),

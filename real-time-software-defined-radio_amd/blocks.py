@@ -359,6 +359,14 @@ class Receiver(_Handle):
         kw.setdefault("ctx", self.ctx)
         return RdsLinkBank(self.S, self._length("rrc_i"), **kw)
 
+    def mpx_spectrum(self, nfft: int = 1024, hop=None, navg: int = 0, **kw) -> "RowSpectrum":
+        """A RowSpectrum sized to this receiver's "demod" rows (one row per stream, the multiplex at
+        design.AUDIO_FS; hop defaults to nfft / 2); feed it with spectrum.process_rx(receiver,
+        out_ptr) after a block and read the rows with mpx_quality."""
+        kw.setdefault("ctx", self.ctx)
+        nfft = int(nfft)
+        return RowSpectrum(self.S, nfft, design.AUDIO_FS, hop=nfft // 2 if hop is None else hop, navg=navg, **kw)
+
     def set_timing(self, on: bool = True):
         """Record HIP events between the receiver's launches (stage_ms)."""
         check(self.lib.sdr_rx_set_timing(self.handle, int(bool(on))), "sdr_rx_set_timing")
@@ -811,6 +819,12 @@ class Spectrum(_Handle):
     _prefix = "sdr_spec"
 
     def __init__(self, nfft: int, fs: float, hop=None, navg: int = 0, window="hann", iq_dtype=np.float32, ctx=None):
+        self._set_geometry(nfft, fs, hop, navg, window)
+        self.u8 = _is_u8(iq_dtype)
+        self._ctx = ctx
+
+    def _set_geometry(self, nfft, fs, hop, navg, window):
+        """The checks and attributes Spectrum and RowSpectrum share (no context is touched)."""
         nfft, fs, navg = int(nfft), float(fs), int(navg)
         if not (np.isfinite(fs) and fs > 0):
             raise ValueError("fs must be positive")
@@ -822,10 +836,8 @@ class Spectrum(_Handle):
         if navg < 0:
             raise ValueError(f"navg={navg} must be 0 (one row) or >= 1")
         w = design.spectrum_window(window, nfft)
-        self.u8 = _is_u8(iq_dtype)
         self.nfft, self.fs, self.hop, self.navg, self.window = nfft, fs, hop, navg, w
         self.scale = float(np.sum(w)) ** 2
-        self._ctx = ctx
 
     @property
     def freqs_hz(self) -> np.ndarray:
@@ -921,3 +933,130 @@ def find_channels(power_row, fs: float, spacing_hz: float, width_hz=None, min_sn
         right = np.r_[power[1:], -np.inf]
         keep &= (power >= left) & (power >= right)
     return FoundChannels(j[keep].astype(np.int64), f[keep], snr[keep])
+
+
+class RowSpectrum(Spectrum):
+    """The one-sided spectrum of `nrows` rows of real float32 samples on the GPU in one call
+    (sdr_rspec, csrc/spectrum.hip) -- a Receiver's demodulated rows, read where the receiver left
+    them: what does each stream hold after demodulation?  With segment s of row q starting at
+    sample s hop and window w,
+
+        X_qs[k]      = sum_{i < nfft} w[i] x_q[s hop + i] exp(-2 pi i k i / nfft),   k = 0 .. nfft / 2
+        out[q][r][k] = (c_k / (navg (sum w)^2)) sum_{s in [r navg, (r + 1) navg)} |X_qs[k]|^2
+
+    with c_0 = c_{nfft/2} = 1 and 2 otherwise: linear power in float32, bin k centred on
+    freqs_hz[k] = k fs / nfft -- scipy.signal.spectrogram(x_q, window=w, nperseg=nfft,
+    noverlap=nfft - hop, detrend=False, return_onesided=True, scaling='spectrum', mode='psd')
+    averaged over groups of navg columns.  nfft, hop, navg, window, scale and rows(n) (per input
+    row) are Spectrum's; nrows: 1 .. 65 535.  Nothing is carried between calls.  The arguments are
+    checked, and the geometry answers, before a context exists.  mpx_quality reads the rows."""
+
+    MAX_ROWS = 65535                                             # include/sdr.h SDR_RSPEC_MAX_ROWS
+    _prefix = "sdr_rspec"
+
+    def __init__(self, nrows: int, nfft: int, fs: float, hop=None, navg: int = 0, window="hann", ctx=None):
+        nrows = int(nrows)
+        if not 1 <= nrows <= self.MAX_ROWS:
+            raise ValueError(f"nrows={nrows} outside [1, {self.MAX_ROWS}]")
+        self._set_geometry(nfft, fs, hop, navg, window)
+        self.nrows, self.nbins = nrows, self.nfft // 2 + 1
+        self._ctx = ctx
+
+    @property
+    def freqs_hz(self) -> np.ndarray:
+        """The nfft / 2 + 1 bin centres, 0 .. fs / 2: k fs / nfft."""
+        return np.arange(self.nbins) * (self.fs / self.nfft)
+
+    def _open(self):
+        if self.handle is None:
+            self.ctx = self._ctx if self._ctx is not None else _lib.get_context()
+            self.lib = self.ctx.lib
+            h = ctypes.c_void_p()
+            check(self.lib.sdr_rspec_create(self.ctx.handle, self.nrows, self.nfft, f64p(self.window), self.hop, self.navg,
+                                            ctypes.byref(h)), "sdr_rspec_create")
+            self.handle = h
+        return self.handle
+
+    def process_dev(self, x_ptr: int, n: int, in_stride: int, out_ptr: int, out_stride=None) -> int:
+        """n samples per row at device pointer x_ptr, rows in_stride floats apart -> per input row
+        `rows` rows of nfft / 2 + 1 float32 at out_ptr, row (q, r) at (q rows + r) out_stride floats
+        (None: nfft / 2 + 1; the floats between rows are not written); async on the context
+        stream.  Returns rows."""
+        n, in_stride = int(n), int(in_stride)
+        rows = self.rows(n)[1]
+        out_stride = self.nbins if out_stride is None else int(out_stride)
+        if in_stride < n:
+            raise ValueError(f"in_stride={in_stride} < n={n}")
+        if out_stride < self.nbins:
+            raise ValueError(f"out_stride={out_stride} < nfft/2+1={self.nbins}")
+        h = self._open()
+        check(self.lib.sdr_rspec_process_dev(h, x_ptr, n, in_stride, out_ptr, out_stride), "sdr_rspec_process_dev")
+        return rows
+
+    def process_rx(self, receiver: "Receiver", out_ptr: int, name: str = "demod", out_stride=None) -> int:
+        """The receiver's latest rows of output `name` (looked up at every call: a pipelined
+        receiver alternates its row sets) -> out_ptr as process_dev.  Returns rows."""
+        if receiver.S != self.nrows:
+            raise ValueError(f"the receiver has {receiver.S} streams, the spectrum {self.nrows} rows")
+        ptr, stride, n = receiver.output_ptr(name)
+        return self.process_dev(ptr, n, stride, out_ptr, out_stride)
+
+    def run(self, x_host) -> np.ndarray:
+        """(nrows, n) real samples from the host -> float32[nrows, rows, nfft / 2 + 1], synchronous
+        (sdr_rspec_run)."""
+        x = np.ascontiguousarray(x_host, dtype=np.float32)
+        if x.ndim != 2 or x.shape[0] != self.nrows:
+            raise ValueError(f"expected an array of shape ({self.nrows}, n)")
+        n = x.shape[1]
+        rows = self.rows(n)[1]
+        out = np.empty((self.nrows, rows, self.nbins), dtype=np.float32)
+        h = self._open()
+        check(self.lib.sdr_rspec_run(h, x.ctypes.data, n, n, out.ctypes.data, self.nbins), "sdr_rspec_run")
+        return out
+
+
+MpxQuality = collections.namedtuple("MpxQuality", "pilot_snr_db rds_snr_db noise_floor stereo rds")
+
+MPX_PILOT_BAND, MPX_PILOT_GUARD = (18.5e3, 19.5e3), ((16e3, 18e3), (20e3, 22e3))
+MPX_RDS_BAND, MPX_RDS_GUARD = (55e3, 59e3), ((60e3, 64e3),)
+
+
+def mpx_quality(power, fs: float = 240e3, min_pilot_db: float = 15.0, min_rds_db: float = 6.0) -> MpxQuality:
+    """A tuner's stereo lamp and signal meter from one-sided spectra of the FM multiplex (host,
+    numpy): RowSpectrum rows of a Receiver's "demod" output, any shape (..., nfft / 2 + 1), bin k
+    centred on k fs / nfft.
+
+    A bin belongs to a band if its centre lies in the closed interval.  A subcarrier's ratio is
+    sum(band) / (median(guard) x bins in band), in dB: the 19 kHz pilot in 18.5 - 19.5 kHz against
+    the gaps 16 - 18 kHz and 20 - 22 kHz on either side of it (above the mono audio, below L-R),
+    the RDS subcarrier in 55 - 59 kHz against 60 - 64 kHz.  noise_floor is the pilot guard's median
+    (linear, per bin); stereo and rds are the ratios against min_pilot_db and min_rds_db.  All five
+    have the shape power.shape[:-1].
+
+    Needs fs / 2 > 64 kHz and bins no wider than 500 Hz (nfft >= 512 at 240 kHz): with wider bins
+    the window's skirts of the audio and of the pilot fill the guard bands."""
+    p = np.asarray(power, dtype=np.float64)
+    fs = float(fs)
+    if p.ndim < 1 or p.shape[-1] < 3:
+        raise ValueError("power: rows of nfft / 2 + 1 bins")
+    if not (np.isfinite(fs) and fs > 0):
+        raise ValueError("fs must be positive")
+    nfft = 2 * (p.shape[-1] - 1)
+    if fs / 2 <= MPX_RDS_GUARD[-1][1]:
+        raise ValueError(f"fs={fs}: the guard band up to {MPX_RDS_GUARD[-1][1]} Hz needs fs / 2 above it")
+    if fs / nfft > 500.0:
+        raise ValueError(f"bins of {fs / nfft:.1f} Hz ({p.shape[-1]} bins at fs={fs}) are wider than 500 Hz")
+    f = np.arange(p.shape[-1]) * (fs / nfft)
+
+    def ratio_db(band, guards):
+        inb = (f >= band[0]) & (f <= band[1])
+        ing = np.zeros(len(f), dtype=bool)
+        for lo, hi in guards:
+            ing |= (f >= lo) & (f <= hi)
+        floor = np.median(p[..., ing], axis=-1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return 10.0 * np.log10(np.sum(p[..., inb], axis=-1) / (floor * np.count_nonzero(inb))), floor
+
+    pilot, floor = ratio_db(MPX_PILOT_BAND, MPX_PILOT_GUARD)
+    rds, _ = ratio_db(MPX_RDS_BAND, MPX_RDS_GUARD)
+    return MpxQuality(pilot, rds, floor, pilot >= float(min_pilot_db), rds >= float(min_rds_db))
