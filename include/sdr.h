@@ -256,6 +256,58 @@ int sdr_audio_out_dev(sdr_ctx* ctx, const float* left, const float* right, int64
                       int nstreams, const double* b, double a1, double* state, float* left_out,
                       float* right_out, int16_t* pcm, int64_t pcm_stride);
 
+/* ---- stereo blend and noise mute from each stream's MPX quality --------------------------
+ * What a tuner does with its signal meter, on the device: sdr_blend_update_dev reads one
+ * one-sided power spectrum per stream (nbins = nfft / 2 + 1 f32, rows `stride` floats apart: what
+ * sdr_rspec_process_dev writes with navg 0 from a receiver's SDR_RX_O_DEMOD rows), computes the
+ * stream's quality in f64 -- bin k, centred on k fs / nfft, belongs to a band if its centre lies
+ * in the closed interval; a ratio is 10 log10(sum(band) / (median(guard) x bins in band)): the
+ * pilot in 18.5 - 19.5 kHz against 16 - 18 kHz and 20 - 22 kHz, RDS in 55 - 59 kHz against
+ * 60 - 64 kHz; the median is the mean of the two middle values for an even count; noise_floor is
+ * the pilot guard's median -- and from it the targets
+ *   target_g = clip((pilot_db - blend_lo_db) / (blend_hi_db - blend_lo_db), 0, 1)
+ *   target_m = clip((mute_hi_db - 10 log10(noise_floor)) / (mute_hi_db - mute_lo_db), 0, 1)
+ * (a NaN gives target 0; mute off: m is 1 always), smoothed for g and m alike:
+ *   prev <- cur;  cur <- cur + k (target - cur),  k = attack if target < cur, else release.
+ * NaN and zero floors give what IEEE arithmetic gives; a NaN in a row reaches that row's values
+ * only.  One launch per update, one wave per stream (csrc/blend.hip); no host synchronisation.
+ * State per stream, f64, device: SDR_BLEND_NSTATE values {pilot_db, rds_db, noise_floor, g_prev,
+ * g, m_prev, m, n_updates}; after create / reset all 0 (mono until a pilot has been seen), except
+ * m_prev = m = 1 with mute off.  sdr_blend_gains_dev: the device array [nstreams][4] =
+ * {g_prev, g, m_prev, m} that sdr_audio_blend_dev ramps over a block.
+ * Parameters (NULL = defaults): blend 15 / 25 dB (15: mpx_quality's lamp threshold), mute off
+ * (mute_lo_db = mute_hi_db = +inf; on: both finite, full volume at or below mute_lo_db, silence at or
+ * above mute_hi_db), attack 1, release 0.25.  SDR_EINVAL: non-finite blend limits, lo >= hi (blend;
+ * mute when on), attack or release outside (0, 1], mute limits neither both finite nor both +inf.
+ * sdr_blend_update_dev, SDR_EINVAL before any device work: NULL power, nbins < 3, stride < nbins,
+ * fs not positive and finite, fs / 2 <= 64 kHz, bins wider than 500 Hz (as mpx_quality), a guard of
+ * more than SDR_BLEND_MAX_GUARD bins.  sdr_blend_reset and sdr_blend_update_dev are asynchronous
+ * on the context stream; sdr_blend_state (host [nstreams][SDR_BLEND_NSTATE]) synchronises. */
+#define SDR_BLEND_NSTATE 8
+#define SDR_BLEND_MAX_GUARD 1024
+typedef struct sdr_blend_params {
+  double blend_lo_db, blend_hi_db, mute_lo_db, mute_hi_db, attack, release;
+} sdr_blend_params;
+typedef struct sdr_blend sdr_blend;
+int  sdr_blend_create(sdr_ctx* ctx, int nstreams, const sdr_blend_params* params, sdr_blend** out);
+void sdr_blend_destroy(sdr_blend* blend);
+int  sdr_blend_reset(sdr_blend* blend);
+int  sdr_blend_update_dev(sdr_blend* blend, const float* power, int nbins, int64_t stride, double fs);
+int  sdr_blend_state(sdr_blend* blend, double* host);
+int  sdr_blend_gains_dev(sdr_blend* blend, const double** dev);
+/* sdr_audio_out_dev with the gains applied in the same pass (same argument rules and launch
+ * count; SDR_EINVAL also for NULL gains_dev): with gains_dev[s] = {g0, g1, m0, m1}, sample i of n
+ * of stream s becomes, in f64 and rounded once to f32,
+ *   t = (i + 1) / n,  g = g0 + (g1 - g0) t,  m = m0 + (m1 - m0) t
+ *   L' = (float)(m ((L + R) / 2 + g (L - R) / 2)),  R' = (float)(m ((L + R) / 2 - g (L - R) / 2))
+ * (mono, right NULL: L' = (float)(m L)), and that f32 is what the section filters, or with b NULL
+ * what is written and converted by the PCM rule.  All gains 1 give L and R (exactly whenever the
+ * f64 sums L + R and L - R are exact: always, unless one channel is below 2^-29 of the other);
+ * g0 = g1 = 0 gives two bit-identical channels. */
+int sdr_audio_blend_dev(sdr_ctx* ctx, const float* left, const float* right, int64_t n, int64_t stride,
+                        int nstreams, const double* b, double a1, double* state, float* left_out,
+                        float* right_out, int16_t* pcm, int64_t pcm_stride, const double* gains_dev);
+
 /* ---- multi-stream block receiver ----------------------------------
  * The per-block loops of model/fmMonoBlock.py:80-173 (mono, stereo; intended L/R combiner)
  * and model/fmRDSblock.py:127-204 (RDS up to the RRC output) for `nstreams` independent
@@ -312,6 +364,21 @@ int sdr_rx_set_pll(sdr_rx* rx, int which /* 0 stereo, 1 RDS */, double freq, dou
  * from every call that names them, and from sdr_rx_pcm), occupy no memory and cost no launch. */
 int sdr_rx_set_deemph(sdr_rx* rx, const double* b, double a1);
 int sdr_rx_pcm(sdr_rx* rx, int16_t** dev, int64_t* stride, int64_t* n);
+/* Stereo blend and noise mute in the audio output stage (off by default; set before the first
+ * block; nfft 0 = off; params NULL = sdr_blend_create's defaults).  Needs SDR_RX_AUDIO, the audio
+ * output stage (sdr_rx_set_deemph) and M >= nfft demod samples per block, nfft a power of two that
+ * sdr_rspec and sdr_blend_update_dev accept at the multiplex rate of 240 kHz (512 .. 8192);
+ * SDR_EINVAL otherwise (M: when the first block fixes the configuration).  Every block then
+ * gets, on the context stream directly before the audio tail, an sdr_rspec of its
+ * SDR_RX_O_DEMOD rows (periodic Hann, hop nfft / 2, navg 0) and an sdr_blend_update_dev of those
+ * spectra, and the tail's sdr_audio_out_dev call becomes sdr_audio_blend_dev with the updated
+ * gains: the block's quality sets the gain its own audio ramps to.  The results land in the
+ * existing _DE rows and the PCM (SDR_RX_O_LEFT_DE / _RIGHT_DE, or SDR_RX_O_AUDIO_DE of a receiver
+ * without SDR_RX_STEREO, which takes the mute gain alone); a stereo receiver's separately kept
+ * SDR_RX_O_AUDIO_DE stays unblended.  The blend's memory is the receiver's own; sdr_rx_reset
+ * resets its state.  sdr_rx_blend_state: sdr_blend_state of the receiver's blend (synchronises). */
+int sdr_rx_set_blend(sdr_rx* rx, const sdr_blend_params* params, int nfft);
+int sdr_rx_blend_state(sdr_rx* rx, double* host /* [nstreams][SDR_BLEND_NSTATE] */);
 int sdr_rx_reset(sdr_rx* rx);                       /* all states back to the stream start */
 int sdr_rx_process_dev(sdr_rx* rx, const void* iq, int64_t iq_stride);   /* async, device IQ */
 int sdr_rx_process(sdr_rx* rx, const void* iq, int64_t iq_stride);       /* sync, host IQ */

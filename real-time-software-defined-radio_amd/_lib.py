@@ -94,6 +94,13 @@ SIGNATURES = {
     "sdr_iir1": (_i32, [_vp, _fp, _i64, _dp, _f64, _dp, _fp]),
     "sdr_iir1_dev": (_i32, [_vp, _vp, _i64, _i64, _i32, _dp, _f64, _vp, _vp, _vp, _i64]),
     "sdr_audio_out_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _dp, _f64, _vp, _vp, _vp, _vp, _i64]),
+    "sdr_audio_blend_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _dp, _f64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "sdr_blend_create": (_i32, [_vp, _i32, _vp, _c.POINTER(_vp)]),
+    "sdr_blend_destroy": (None, [_vp]),
+    "sdr_blend_reset": (_i32, [_vp]),
+    "sdr_blend_update_dev": (_i32, [_vp, _vp, _i32, _i64, _f64]),
+    "sdr_blend_state": (_i32, [_vp, _dp]),
+    "sdr_blend_gains_dev": (_i32, [_vp, _c.POINTER(_vp)]),
     "sdr_psd": (_i32, [_vp, _dp, _i64, _i32, _f64, _dp]),
     "sdr_psd_dev": (_i32, [_vp, _vp, _i32, _i64, _i32, _f64, _vp]),
     "sdr_dft": (_i32, [_vp, _dp, _i64, _dp]),
@@ -104,6 +111,8 @@ SIGNATURES = {
     "sdr_rx_set_pll": (_i32, [_vp, _i32, _f64, _f64, _f64, _f64, _f64]),
     "sdr_rx_reset": (_i32, [_vp]),
     "sdr_rx_set_deemph": (_i32, [_vp, _dp, _f64]),
+    "sdr_rx_set_blend": (_i32, [_vp, _vp, _i32]),
+    "sdr_rx_blend_state": (_i32, [_vp, _dp]),
     "sdr_rx_pcm": (_i32, [_vp, _c.POINTER(_vp), _c.POINTER(_i64), _c.POINTER(_i64)]),
     "sdr_rx_process_dev": (_i32, [_vp, _vp, _i64]),
     "sdr_rx_process": (_i32, [_vp, _vp, _i64]),

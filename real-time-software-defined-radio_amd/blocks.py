@@ -161,14 +161,31 @@ class Receiver(_Handle):
     The receiver then also produces "audio_de" ("left_de", "right_de" with stereo=True) -- the
     audio rows through design.deemphasis_coeffs(deemphasis, 240 kHz / audio_decim) on the device
     (sdr_rx_set_deemph), state carried from block to block -- and pcm(), the block's interleaved
-    int16 samples; process()'s default outputs include the de-emphasised rows."""
+    int16 samples; process()'s default outputs include the de-emphasised rows.
+
+    blend: True (BlendParams' defaults) or a BlendParams (default False: off).  Needs deemphasis.
+    Every block's "demod" rows then go through a RowSpectrum (blend_nfft, hop blend_nfft / 2,
+    navg 0) and a BlendControl on the device, and the audio output stage ramps "left_de" /
+    "right_de" and pcm() to the resulting stereo and mute gains (sdr_rx_set_blend; without stereo
+    "audio_de" takes the mute gain; a stereo receiver's "audio_de" stays unblended).
+    blend_state() reads the quality and gains back."""
 
     _prefix = "sdr_rx"
 
     def __init__(self, nstreams: int, block_complex: int, *, mono: bool = True, stereo: bool = False,
                  rds: bool = False, iq_dtype=np.uint8, rf_coeff=None, audio_coeff=None, stereo_taps: int = 151,
                  rds_taps: int = 151, rf_decim: int = 10, audio_decim: int = 5, pipeline: bool = False,
-                 depth: int = 1, keep=None, deemphasis=None, ctx=None):
+                 depth: int = 1, keep=None, deemphasis=None, blend=False, blend_nfft: int = 1024, ctx=None):
+        # blend: its arguments are checked before a context exists
+        self.blend = None if blend is False or blend is None else _blend_params(blend)
+        self.blend_nfft = int(blend_nfft)
+        if self.blend is not None:
+            if deemphasis is None or not (mono or stereo):
+                raise ValueError("blend needs the audio output stage: an audio output and deemphasis=tau")
+            if not 512 <= self.blend_nfft <= Spectrum.MAX_NFFT or self.blend_nfft & (self.blend_nfft - 1):
+                raise ValueError(f"blend_nfft={self.blend_nfft} must be a power of two in [512, {Spectrum.MAX_NFFT}]")
+            if -(-int(block_complex) // int(rf_decim)) < self.blend_nfft:
+                raise ValueError(f"blend_nfft={self.blend_nfft} exceeds the block's demod samples")
         self.ctx = ctx if ctx is not None else _lib.get_context()
         self.lib = self.ctx.lib
         self.S, self.B = int(nstreams), int(block_complex)
@@ -212,6 +229,8 @@ class Receiver(_Handle):
             self.deemph_coeffs = (b, a)
             check(self.lib.sdr_rx_set_deemph(self.handle, f64p(np.ascontiguousarray(b)), float(a[1])),
                   "sdr_rx_set_deemph")
+        if self.blend is not None:
+            check(self.lib.sdr_rx_set_blend(self.handle, ctypes.byref(self.blend._c()), self.blend_nfft), "sdr_rx_set_blend")
         if keep is not None:
             self.set_keep(keep)
         self.M = (self.B + rf_decim - 1) // rf_decim
@@ -332,6 +351,15 @@ class Receiver(_Handle):
         buf = np.empty((self.S, st.value), dtype=np.int16)
         check(self.lib.sdr_memcpy_d2h(self.ctx.handle, buf.ctypes.data, p.value, buf.nbytes), "sdr_memcpy_d2h")
         return np.ascontiguousarray(buf[:, :n.value])
+
+    def blend_state(self) -> "BlendState":
+        """The blend's quality of the latest block and the gains its audio ramped to
+        (sdr_rx_blend_state; synchronises): BlendControl.state().  Needs blend."""
+        if self.blend is None:
+            raise ValueError("blend_state needs a receiver with blend=True")
+        raw = np.empty((self.S, BlendControl.NSTATE))
+        check(self.lib.sdr_rx_blend_state(self.handle, f64p(raw)), "sdr_rx_blend_state")
+        return _blend_state(raw)
 
     def state(self):
         """Carried states: (demod prev_phase [S], stereo PLL [S, 6], RDS PLL [S, 6])."""
@@ -1060,3 +1088,140 @@ def mpx_quality(power, fs: float = 240e3, min_pilot_db: float = 15.0, min_rds_db
     pilot, floor = ratio_db(MPX_PILOT_BAND, MPX_PILOT_GUARD)
     rds, _ = ratio_db(MPX_RDS_BAND, MPX_RDS_GUARD)
     return MpxQuality(pilot, rds, floor, pilot >= float(min_pilot_db), rds >= float(min_rds_db))
+
+
+class _BlendParamsC(ctypes.Structure):                           # include/sdr.h sdr_blend_params
+    _fields_ = [(n, ctypes.c_double) for n in ("blend_lo_db", "blend_hi_db", "mute_lo_db", "mute_hi_db", "attack", "release")]
+
+
+class BlendParams(collections.namedtuple("BlendParams", "blend_lo_db blend_hi_db mute_lo_db mute_hi_db attack release")):
+    """The gain control's parameters (sdr_blend_params).  The stereo gain goes from 0 at a pilot
+    ratio of blend_lo_db (15: mpx_quality's lamp threshold) to 1 at blend_hi_db; the mute gain from
+    1 at a noise floor of mute_lo_db (10 log10 of mpx_quality's noise_floor) to 0 at mute_hi_db,
+    both +inf (the default): mute off.  attack / release: the share of the way to its target a
+    gain moves per update when the target is below / not below it, in (0, 1]."""
+    __slots__ = ()
+
+    def __new__(cls, blend_lo_db=15.0, blend_hi_db=25.0, mute_lo_db=np.inf, mute_hi_db=np.inf, attack=1.0, release=0.25):
+        p = super().__new__(cls, *(float(v) for v in (blend_lo_db, blend_hi_db, mute_lo_db, mute_hi_db, attack, release)))
+        if not (np.isfinite(p.blend_lo_db) and np.isfinite(p.blend_hi_db) and p.blend_lo_db < p.blend_hi_db):
+            raise ValueError(f"blend limits {p.blend_lo_db}, {p.blend_hi_db} dB: finite, lo < hi")
+        if not (0.0 < p.attack <= 1.0 and 0.0 < p.release <= 1.0):
+            raise ValueError(f"attack {p.attack}, release {p.release} outside (0, 1]")
+        if not (p.mute_on and p.mute_lo_db < p.mute_hi_db) and not (p.mute_lo_db == np.inf and p.mute_hi_db == np.inf):
+            raise ValueError(f"mute limits {p.mute_lo_db}, {p.mute_hi_db} dB: both +inf (off), or finite with lo < hi")
+        return p
+
+    @property
+    def mute_on(self) -> bool:
+        return bool(np.isfinite(self.mute_lo_db) and np.isfinite(self.mute_hi_db))
+
+    def _c(self):
+        return _BlendParamsC(*self)
+
+
+def _blend_params(params):
+    """A `params` argument: None (the defaults), a BlendParams, or the six values of one."""
+    if params is None or params is True:
+        return BlendParams()
+    return params if isinstance(params, BlendParams) else BlendParams(*params)
+
+
+def _check_mpx_bins(nbins: int, fs: float):
+    """mpx_quality's conditions on a spectrum of nbins bins at fs, and the gain control's cap on
+    its guard bands (SDR_BLEND_MAX_GUARD bins each)."""
+    nbins, fs = int(nbins), float(fs)
+    if nbins < 3:
+        raise ValueError("power: rows of nfft / 2 + 1 bins")
+    if not (np.isfinite(fs) and fs > 0):
+        raise ValueError("fs must be positive")
+    nfft = 2 * (nbins - 1)
+    if fs / 2 <= MPX_RDS_GUARD[-1][1]:
+        raise ValueError(f"fs={fs}: the guard band up to {MPX_RDS_GUARD[-1][1]} Hz needs fs / 2 above it")
+    if fs / nfft > 500.0:
+        raise ValueError(f"bins of {fs / nfft:.1f} Hz ({nbins} bins at fs={fs}) are wider than 500 Hz")
+    f = np.arange(nbins) * (fs / nfft)
+    for guards in (MPX_PILOT_GUARD, MPX_RDS_GUARD):
+        if sum(np.count_nonzero((f >= lo) & (f <= hi)) for lo, hi in guards) > BlendControl.MAX_GUARD:
+            raise ValueError(f"{nbins} bins at fs={fs}: a guard of more than {BlendControl.MAX_GUARD} bins")
+
+
+BlendState = collections.namedtuple("BlendState", "pilot_snr_db rds_snr_db noise_floor stereo_gain mute_gain")
+
+
+class BlendControl(_Handle):
+    """Stereo blend and noise mute gains of `nstreams` streams from their multiplex spectra, on the
+    GPU (sdr_blend, csrc/blend.hip): update_dev reads one RowSpectrum row (navg=0) per stream,
+    computes mpx_quality's pilot and RDS ratios and noise floor in f64, and moves each stream's
+    gains towards
+
+        target_g = clip((pilot_snr_db - blend_lo_db) / (blend_hi_db - blend_lo_db), 0, 1)
+        target_m = clip((mute_hi_db - 10 log10(noise_floor)) / (mute_hi_db - mute_lo_db), 0, 1)
+
+    by cur += k (target - cur), k = attack when the target is below cur, else release (a NaN gives
+    target 0; mute off: m = 1).  One launch, one wave per stream, nothing comes back to the host;
+    audio_blend_dev ramps the rows from the previous gains to the new ones (gains_ptr).  After
+    creation and reset(): g = 0 (mono until a pilot has been seen), m = 0 with mute on, else 1.
+    The arguments are checked before a context exists."""
+
+    MAX_GUARD = 1024                                             # include/sdr.h SDR_BLEND_MAX_GUARD
+    NSTATE = 8                                                   # SDR_BLEND_NSTATE
+    _prefix = "sdr_blend"
+
+    def __init__(self, nstreams: int, params=None, ctx=None):
+        nstreams = int(nstreams)
+        if not 1 <= nstreams <= 65535:
+            raise ValueError(f"nstreams={nstreams} outside [1, 65535]")
+        self.nstreams, self.params = nstreams, _blend_params(params)
+        self._ctx = ctx
+
+    def _open(self):
+        if self.handle is None:
+            self.ctx = self._ctx if self._ctx is not None else _lib.get_context()
+            self.lib = self.ctx.lib
+            h = ctypes.c_void_p()
+            check(self.lib.sdr_blend_create(self.ctx.handle, self.nstreams, ctypes.byref(self.params._c()), ctypes.byref(h)),
+                  "sdr_blend_create")
+            self.handle = h
+        return self.handle
+
+    def update_dev(self, power_ptr: int, nbins: int, stride: int, fs: float):
+        """One update from nstreams rows of nbins float32 power bins at device pointer power_ptr,
+        `stride` floats apart (bin k centred on k fs / (2 (nbins - 1))); async on the context stream."""
+        nbins, stride, fs = int(nbins), int(stride), float(fs)
+        if not power_ptr:
+            raise ValueError("power_ptr is NULL")
+        _check_mpx_bins(nbins, fs)
+        if stride < nbins:
+            raise ValueError(f"stride={stride} < nbins={nbins}")
+        h = self._open()
+        check(self.lib.sdr_blend_update_dev(h, power_ptr, nbins, stride, fs), "sdr_blend_update_dev")
+
+    def raw_state(self) -> np.ndarray:
+        """(nstreams, 8) float64: pilot_db, rds_db, noise_floor, g_prev, g, m_prev, m, n_updates
+        (sdr_blend_state; synchronises)."""
+        out = np.empty((self.nstreams, self.NSTATE))
+        h = self._open()
+        check(self.lib.sdr_blend_state(h, f64p(out)), "sdr_blend_state")
+        return out
+
+    def state(self) -> BlendState:
+        """The latest update's quality and the gains now in force, arrays of nstreams values."""
+        return _blend_state(self.raw_state())
+
+    @property
+    def gains_ptr(self) -> int:
+        """The device array (nstreams, 4) float64 {g_prev, g, m_prev, m} (sdr_blend_gains_dev)."""
+        p = ctypes.c_void_p()
+        h = self._open()
+        check(self.lib.sdr_blend_gains_dev(h, ctypes.byref(p)), "sdr_blend_gains_dev")
+        return p.value
+
+    def reset(self):
+        """Back to the state after creation (async)."""
+        h = self._open()
+        check(self.lib.sdr_blend_reset(h), "sdr_blend_reset")
+
+
+def _blend_state(raw) -> BlendState:
+    return BlendState(raw[:, 0].copy(), raw[:, 1].copy(), raw[:, 2].copy(), raw[:, 4].copy(), raw[:, 6].copy())

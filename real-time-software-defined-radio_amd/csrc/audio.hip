@@ -107,7 +107,34 @@ __device__ __forceinline__ RowSel row_of(const IirLaunch& a, int s, int ch) {
   return r;
 }
 
+// BLEND: a lane's 8 samples of both channels (right unused with nch == 1) through the stream's
+// gain ramp gn = {g0, g1, m0, m1} (IirLaunch::gains), in f64 and rounded once.  reduce and apply
+// both form their samples here, so both see the same f32 values.
+__device__ __forceinline__ void blend8(const double* __restrict__ gn, int64_t i0, int64_t n, int nch, float (&l)[IIR_ITEMS],
+                                       float (&r)[IIR_ITEMS]) {
+  const double g0 = gn[0], dg = gn[1] - g0, m0 = gn[2], dm = gn[3] - m0, dn = (double)n;
+  double g[IIR_ITEMS], m[IIR_ITEMS];
+#pragma unroll
+  for (int j = 0; j < IIR_ITEMS; ++j) {
+    const double t = (double)(i0 + j + 1) / dn;
+    g[j] = g0 + dg * t;
+    m[j] = m0 + dm * t;
+  }
+  if (nch == 2) {
+#pragma unroll
+    for (int j = 0; j < IIR_ITEMS; ++j) {
+      const double mid = ((double)l[j] + (double)r[j]) / 2.0, side = ((double)l[j] - (double)r[j]) / 2.0;
+      l[j] = (float)(m[j] * (mid + g[j] * side));
+      r[j] = (float)(m[j] * (mid - g[j] * side));
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < IIR_ITEMS; ++j) l[j] = (float)(m[j] * (double)l[j]);
+  }
+}
+
 // reduce: the zero-state end state of every tile but each row's last -> agg[row][tile]
+template <bool BLEND>
 __global__ __launch_bounds__(IIR_T) void iir1_reduce_kernel(const IirLaunch a) {
   __shared__ double wagg[2][IIR_NW];
   const int tid = threadIdx.x, s = blockIdx.y;
@@ -116,6 +143,7 @@ __global__ __launch_bounds__(IIR_T) void iir1_reduce_kernel(const IirLaunch a) {
 #pragma unroll
   for (int ch = 0; ch < 2; ++ch)
     if (ch < a.nch) load8(row_of(a, s, ch).x, i0, IIR_ITEMS, a.vec_x != 0, xs[ch]);
+  if (BLEND) blend8(a.gains + 4 * (int64_t)s, i0, a.n, a.nch, xs[0], xs[1]);
 #pragma unroll
   for (int ch = 0; ch < 2; ++ch) {
     if (ch >= a.nch) break;
@@ -182,6 +210,7 @@ __global__ __launch_bounds__(64) void iir1_carry_kernel(const IirLaunch a) {
 }
 
 // apply: every tile from its entering state -> the f32 rows, the interleaved PCM, the end states
+template <bool BLEND>
 __global__ __launch_bounds__(IIR_T) void iir1_apply_kernel(const IirLaunch a) {
   __shared__ double wagg[2][IIR_NW], cin[2];
   const int tid = threadIdx.x, s = blockIdx.y;
@@ -195,6 +224,7 @@ __global__ __launch_bounds__(IIR_T) void iir1_apply_kernel(const IirLaunch a) {
 #pragma unroll
   for (int ch = 0; ch < 2; ++ch)
     if (ch < a.nch) load8(row_of(a, s, ch).x, i0, len, a.vec_x != 0, xs[ch]);
+  if (BLEND) blend8(a.gains + 4 * (int64_t)s, i0, a.n, a.nch, xs[0], xs[1]);
 #pragma unroll
   for (int ch = 0; ch < 2; ++ch) {
     if (ch >= a.nch) break;
@@ -272,14 +302,17 @@ hipError_t sdr_launch_iir1(const IirLaunch& in, hipStream_t st) {
   a.vec_y = a.y_stride % 4 == 0 && (a.y[0] == nullptr || al16(a.y[0])) && (a.y[1] == nullptr || al16(a.y[1]));
   a.vec_pcm = a.pcm != nullptr && al16(a.pcm) && a.pcm_stride % 8 == 0;
   const dim3 blk(IIR_T);
+  const bool blend = a.gains != nullptr;
   if (a.filter && a.ntiles > 1) {
     if (a.agg == nullptr || a.carry == nullptr) return hipErrorInvalidValue;
     a.K = (a.ntiles + 63) / 64;
     const double p = -a.a1;
     for (int k = 0; k < 6; ++k) a.q[k] = std::pow(p, (double)IIR_TILE * (double)a.K * (double)(1 << k));
-    hipLaunchKernelGGL(iir1_reduce_kernel, dim3((unsigned)(a.ntiles - 1), (unsigned)a.nstreams), blk, 0, st, a);
+    hipLaunchKernelGGL(blend ? iir1_reduce_kernel<true> : iir1_reduce_kernel<false>,
+                       dim3((unsigned)(a.ntiles - 1), (unsigned)a.nstreams), blk, 0, st, a);
     hipLaunchKernelGGL(iir1_carry_kernel, dim3((unsigned)(a.nstreams * a.nch)), dim3(64), 0, st, a);
   }
-  hipLaunchKernelGGL(iir1_apply_kernel, dim3((unsigned)a.ntiles, (unsigned)a.nstreams), blk, 0, st, a);
+  hipLaunchKernelGGL(blend ? iir1_apply_kernel<true> : iir1_apply_kernel<false>, dim3((unsigned)a.ntiles, (unsigned)a.nstreams),
+                     blk, 0, st, a);
   return hipGetLastError();
 }

@@ -728,20 +728,24 @@ int sdr_iir1_dev(sdr_ctx* c, const float* x, int64_t n, int64_t x_stride, int ns
   return run_iir1(c, a, b, a1, "sdr_iir1_dev");
 }
 
-int sdr_audio_out_dev(sdr_ctx* c, const float* left, const float* right, int64_t n, int64_t stride, int nstreams,
-                      const double* b, double a1, double* state, float* left_out, float* right_out, int16_t* pcm,
-                      int64_t pcm_stride) {
+}  // extern "C"
+
+namespace {
+// sdr_audio_out_dev (gains NULL) and sdr_audio_blend_dev: one set of argument rules, one launch chain
+int audio_out(sdr_ctx* c, const float* left, const float* right, int64_t n, int64_t stride, int nstreams, const double* b,
+              double a1, double* state, float* left_out, float* right_out, int16_t* pcm, int64_t pcm_stride,
+              const double* gains, const char* what) {
   CHECK_CTX(c);
   if (n < 1 || nstreams < 1 || nstreams > 65535)
-    return fail(SDR_EINVAL, "sdr_audio_out_dev: n %lld, nstreams %d", (long long)n, nstreams);
-  if (left == nullptr) return fail(SDR_EINVAL, "sdr_audio_out_dev: left is NULL");
-  if (stride < n) return fail(SDR_EINVAL, "sdr_audio_out_dev: stride %lld shorter than the row (%lld)", (long long)stride, (long long)n);
+    return fail(SDR_EINVAL, "%s: n %lld, nstreams %d", what, (long long)n, nstreams);
+  if (left == nullptr) return fail(SDR_EINVAL, "%s: left is NULL", what);
+  if (stride < n) return fail(SDR_EINVAL, "%s: stride %lld shorter than the row (%lld)", what, (long long)stride, (long long)n);
   if (pcm != nullptr && pcm_stride < 2 * n)
-    return fail(SDR_EINVAL, "sdr_audio_out_dev: pcm_stride %lld < 2 n (%lld)", (long long)pcm_stride, (long long)(2 * n));
-  if (b != nullptr && state == nullptr) return fail(SDR_EINVAL, "sdr_audio_out_dev: a filter needs its state");
+    return fail(SDR_EINVAL, "%s: pcm_stride %lld < 2 n (%lld)", what, (long long)pcm_stride, (long long)(2 * n));
+  if (b != nullptr && state == nullptr) return fail(SDR_EINVAL, "%s: a filter needs its state", what);
   if (left_out == nullptr && right_out == nullptr && pcm == nullptr)
-    return fail(SDR_EINVAL, "sdr_audio_out_dev: no output requested");
-  if (right == nullptr && right_out != nullptr) return fail(SDR_EINVAL, "sdr_audio_out_dev: right_out without right");
+    return fail(SDR_EINVAL, "%s: no output requested", what);
+  if (right == nullptr && right_out != nullptr) return fail(SDR_EINVAL, "%s: right_out without right", what);
   TRY(set_dev(c));
   IirLaunch a{};
   a.x[0] = left;
@@ -758,7 +762,145 @@ int sdr_audio_out_dev(sdr_ctx* c, const float* left, const float* right, int64_t
   a.y_stride = stride;
   a.pcm = pcm;
   a.pcm_stride = pcm_stride;
-  return run_iir1(c, a, b, a1, "sdr_audio_out_dev");
+  a.gains = gains;
+  return run_iir1(c, a, b, a1, what);
+}
+}  // namespace
+
+extern "C" {
+
+int sdr_audio_out_dev(sdr_ctx* c, const float* left, const float* right, int64_t n, int64_t stride, int nstreams,
+                      const double* b, double a1, double* state, float* left_out, float* right_out, int16_t* pcm,
+                      int64_t pcm_stride) {
+  return audio_out(c, left, right, n, stride, nstreams, b, a1, state, left_out, right_out, pcm, pcm_stride, nullptr,
+                   "sdr_audio_out_dev");
+}
+
+int sdr_audio_blend_dev(sdr_ctx* c, const float* left, const float* right, int64_t n, int64_t stride, int nstreams,
+                        const double* b, double a1, double* state, float* left_out, float* right_out, int16_t* pcm,
+                        int64_t pcm_stride, const double* gains_dev) {
+  if (gains_dev == nullptr) return fail(SDR_EINVAL, "sdr_audio_blend_dev: gains_dev is NULL");
+  return audio_out(c, left, right, n, stride, nstreams, b, a1, state, left_out, right_out, pcm, pcm_stride, gains_dev,
+                   "sdr_audio_blend_dev");
+}
+
+}  // extern "C"
+
+// ---- quality and gain control (blend.hip) ---------------------------------------------------
+namespace sdrint {
+int blend_params(const sdr_blend_params* params, sdr_blend_params* out, bool* mute_on, const char* what) {
+  sdr_blend_params p = {15.0, 25.0, INFINITY, INFINITY, 1.0, 0.25};
+  if (params != nullptr) p = *params;
+  if (!std::isfinite(p.blend_lo_db) || !std::isfinite(p.blend_hi_db) || !(p.blend_lo_db < p.blend_hi_db))
+    return fail(SDR_EINVAL, "%s: blend limits %g, %g dB: finite, lo < hi", what, p.blend_lo_db, p.blend_hi_db);
+  if (!(p.attack > 0.0 && p.attack <= 1.0) || !(p.release > 0.0 && p.release <= 1.0))
+    return fail(SDR_EINVAL, "%s: attack %g, release %g outside (0, 1]", what, p.attack, p.release);
+  const bool off = p.mute_lo_db == INFINITY && p.mute_hi_db == INFINITY;
+  const bool on = std::isfinite(p.mute_lo_db) && std::isfinite(p.mute_hi_db);
+  if (!(off || (on && p.mute_lo_db < p.mute_hi_db)))
+    return fail(SDR_EINVAL, "%s: mute limits %g, %g dB: both +inf (off), or finite with lo < hi", what, p.mute_lo_db, p.mute_hi_db);
+  *out = p;
+  *mute_on = on;
+  return SDR_OK;
+}
+}  // namespace sdrint
+
+struct sdr_blend {
+  sdr_ctx* c = nullptr;
+  int S = 0, mute = 0;
+  sdr_blend_params prm = {};
+  double *state = nullptr, *gains = nullptr;   // device: [S][SDR_BLEND_NSTATE], [S][4] (one allocation)
+  double bands_fs = 0.0; int bands_nbins = 0;  // the (fs, nbins) `bands` was computed for
+  BlendBands bands = {};
+};
+
+extern "C" {
+
+int sdr_blend_create(sdr_ctx* c, int nstreams, const sdr_blend_params* params, sdr_blend** out) {
+  CHECK_CTX(c);
+  if (out == nullptr) return fail(SDR_EINVAL, "sdr_blend_create: out is NULL");
+  *out = nullptr;
+  if (nstreams < 1 || nstreams > 65535) return fail(SDR_EINVAL, "sdr_blend_create: nstreams=%d outside [1, 65535]", nstreams);
+  sdr_blend_params p;
+  bool on = false;
+  TRY(blend_params(params, &p, &on, "sdr_blend_create"));
+  sdr_blend* d = new (std::nothrow) sdr_blend();
+  if (d == nullptr) return fail(SDR_ENOMEM, "sdr_blend_create: out of host memory");
+  d->c = c; d->S = nstreams; d->mute = on ? 1 : 0; d->prm = p;
+  int rc = set_dev(c);
+  if (rc == SDR_OK) {
+    hipError_t e = hipMalloc(&d->state, sizeof(double) * (SDR_BLEND_NSTATE + 4) * (size_t)nstreams);
+    if (e != hipSuccess) rc = create_failed(e, "sdr_blend_create");
+  }
+  if (rc == SDR_OK) {
+    d->gains = d->state + (size_t)SDR_BLEND_NSTATE * nstreams;
+    rc = sdr_blend_reset(d);
+  }
+  if (rc != SDR_OK) {
+    sdr_blend_destroy(d);
+    return rc;
+  }
+  *out = d;
+  return SDR_OK;
+}
+
+void sdr_blend_destroy(sdr_blend* d) {
+  if (d == nullptr) return;
+  if (d->c != nullptr && d->state != nullptr) {
+    (void)hipSetDevice(d->c->device);
+    (void)hipStreamSynchronize(d->c->stream);
+    (void)hipFree(d->state);
+  }
+  delete d;
+}
+
+int sdr_blend_reset(sdr_blend* d) {
+  if (d == nullptr) return fail(SDR_EINVAL, "sdr_blend_reset: object is NULL");
+  TRY(set_dev(d->c));
+  HIP_TRY(sdr_launch_blend_reset(d->state, d->gains, d->S, d->mute, d->c->stream));
+  return SDR_OK;
+}
+
+int sdr_blend_update_dev(sdr_blend* d, const float* power, int nbins, int64_t stride, double fs) {
+  if (d == nullptr) return fail(SDR_EINVAL, "sdr_blend_update_dev: object is NULL");
+  if (power == nullptr) return fail(SDR_EINVAL, "sdr_blend_update_dev: power is NULL");
+  if (reinterpret_cast<uintptr_t>(power) % 4 != 0) return fail(SDR_EINVAL, "sdr_blend_update_dev: power is not 4-byte aligned");
+  if (nbins < 3 || stride < nbins)
+    return fail(SDR_EINVAL, "sdr_blend_update_dev: nbins=%d (>= 3), stride=%lld (>= nbins)", nbins, (long long)stride);
+  if (!(std::isfinite(fs) && fs > 0.0)) return fail(SDR_EINVAL, "sdr_blend_update_dev: fs must be positive");
+  if (fs / 2.0 <= 64e3) return fail(SDR_EINVAL, "sdr_blend_update_dev: fs=%g: the guard band up to 64 kHz needs fs / 2 above it", fs);
+  if (fs / (double)(2 * (nbins - 1)) > 500.0)
+    return fail(SDR_EINVAL, "sdr_blend_update_dev: bins of %.1f Hz (%d bins at fs=%g) are wider than 500 Hz",
+                fs / (double)(2 * (nbins - 1)), nbins, fs);
+  if (d->bands_fs != fs || d->bands_nbins != nbins) {
+    BlendBands bd;
+    if (!sdr_blend_bands(fs, nbins, &bd))
+      return fail(SDR_EINVAL, "sdr_blend_update_dev: %d bins at fs=%g: a guard of more than %d bins", nbins, fs, SDR_BLEND_MAX_GUARD);
+    d->bands = bd; d->bands_fs = fs; d->bands_nbins = nbins;
+  }
+  TRY(set_dev(d->c));
+  BlendLaunch a{};
+  a.power = power; a.stride = stride; a.nstreams = d->S; a.bd = d->bands;
+  a.blend_lo = d->prm.blend_lo_db; a.blend_hi = d->prm.blend_hi_db;
+  a.mute_lo = d->prm.mute_lo_db; a.mute_hi = d->prm.mute_hi_db;
+  a.attack = d->prm.attack; a.release = d->prm.release; a.mute = d->mute;
+  a.state = d->state; a.gains = d->gains;
+  HIP_TRY(sdr_launch_blend_update(a, d->c->stream));
+  return SDR_OK;
+}
+
+int sdr_blend_state(sdr_blend* d, double* host) {
+  if (d == nullptr || host == nullptr) return fail(SDR_EINVAL, "sdr_blend_state: NULL argument");
+  TRY(set_dev(d->c));
+  HIP_TRY(hipMemcpyAsync(host, d->state, sizeof(double) * SDR_BLEND_NSTATE * (size_t)d->S, hipMemcpyDeviceToHost, d->c->stream));
+  HIP_TRY(hipStreamSynchronize(d->c->stream));
+  return SDR_OK;
+}
+
+int sdr_blend_gains_dev(sdr_blend* d, const double** dev) {
+  if (d == nullptr || dev == nullptr) return fail(SDR_EINVAL, "sdr_blend_gains_dev: NULL argument");
+  *dev = d->gains;
+  return SDR_OK;
 }
 
 // ================================================================================

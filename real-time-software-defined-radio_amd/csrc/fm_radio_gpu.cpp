@@ -39,6 +39,9 @@
 // elsewhere; default off -- the reference has none) and the int16 conversion on the
 // device: the final L / R rows go through libsdr's audio output stage (the receiver's own in mode
 // 0, sdr_audio_out_dev in mode 1) and only the interleaved int16 PCM comes back.
+// --blend (mode 0 stereo with --deemph): stereo blend on the device from each block's pilot ratio
+// (sdr_rx_set_blend with its default parameters, a 1 024-point multiplex spectrum): mono below a
+// pilot ratio of 15 dB, full stereo above 25 dB; the mute stays off.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -124,7 +127,7 @@ struct Dev {
 }  // namespace
 
 int main(int argc, char** argv) {
-  bool mono = false, print_taps = false, rds = false, resync = false;
+  bool mono = false, print_taps = false, rds = false, resync = false, blend = false;
   int rf_taps = 151, mode = 0, deemph = 0;
   long long max_blocks = -1;
   for (int i = 1; i < argc; ++i) {
@@ -132,6 +135,7 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--rds")) rds = true;
     else if (!std::strcmp(argv[i], "--resync")) resync = true;
     else if (!std::strcmp(argv[i], "--print-taps")) print_taps = true;
+    else if (!std::strcmp(argv[i], "--blend")) blend = true;
     else if (!std::strcmp(argv[i], "--rf-taps") && i + 1 < argc) rf_taps = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--blocks") && i + 1 < argc) max_blocks = std::atoll(argv[++i]);
     else if (!std::strcmp(argv[i], "--mode") && i + 1 < argc) mode = std::atoi(argv[++i]);
@@ -139,7 +143,7 @@ int main(int argc, char** argv) {
              (!std::strcmp(argv[i + 1], "50") || !std::strcmp(argv[i + 1], "75"))) deemph = std::atoi(argv[++i]);
     else {
       std::fprintf(stderr, "usage: fm_radio_gpu [--mode 0|1] [--mono] [--rds [--resync]] [--rf-taps N] [--blocks N] "
-                           "[--deemph 50|75] [--print-taps] < iq_u8 > pcm_s16le_stereo\n");
+                           "[--deemph 50|75 [--blend]] [--print-taps] < iq_u8 > pcm_s16le_stereo\n");
       return 2;
     }
   }
@@ -149,6 +153,10 @@ int main(int argc, char** argv) {
   }
   if (mode == 1 && rds) {
     std::fprintf(stderr, "fm_radio_gpu: --rds is a mode-0 feature (src/fm_radio.cpp:321-324)\n");
+    return 2;
+  }
+  if (blend && (mode != 0 || mono || !deemph)) {
+    std::fprintf(stderr, "fm_radio_gpu: --blend needs --deemph 50|75 in mode 0 stereo\n");
     return 2;
   }
   if (rf_taps < 3 || rf_taps > SDR_MAX_TAPS_ABI) {
@@ -285,6 +293,7 @@ int main(int argc, char** argv) {
         {SDR_RX_F_RDS_LPF, &rlp_b}, {SDR_RX_F_RDS_ANTI, &ran_b}, {SDR_RX_F_RDS_RRC, &rrc_b}};
     for (const auto& f : taps) ck(sdr_rx_set_filter(rx, f.first, f.second->data(), (int)f.second->size()), "taps");
     if (deemph) ck(sdr_rx_set_deemph(rx, de_b, de_a1), "sdr_rx_set_deemph");
+    if (blend) ck(sdr_rx_set_blend(rx, nullptr, 1024), "sdr_rx_set_blend");
     float* p;
     int64_t stride, n;
     ck(sdr_rx_output(rx, mono ? SDR_RX_O_AUDIO : SDR_RX_O_LEFT, &p, &stride, &n), "output");

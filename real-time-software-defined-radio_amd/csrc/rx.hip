@@ -107,9 +107,19 @@ struct sdr_rx : RxLayout {             // M, A, R, the rows' lengths and strides
   double* de_state = nullptr;          // [S][2]: left (mono without SDR_RX_STEREO), right
   double* de_mono = nullptr;           // [S]: the mono row of a stereo receiver
   int16_t *pcms[3] = {}, *pcm = nullptr;   // interleaved L R rows, pcm_stride int16 apart, per row set; the latest block's
+  // sdr_rx_set_blend: the demod rows' spectra -> the gain control -> the audio tail's gains (blend.hip),
+  // on the context stream directly before the tail; allocations of their own
+  int bl_nfft = 0;                     // 0: off
+  sdr_blend_params bl_prm = {};        // checked, defaults filled in
+  sdr_rspec* bl_spec = nullptr;
+  sdr_blend* bl = nullptr;
+  float* bl_power = nullptr;           // [S][bl_nfft / 2 + 1]
+  const double* bl_gains = nullptr;    // sdr_blend_gains_dev
 };
 
 namespace {
+
+constexpr double kMpxFs = 240e3;     // the multiplex rate sdr_rx_set_blend's spectra assume (the PLLs' default Fs)
 
 PllCfg pll_cfg(double freq, double fs, double scale, double adj, double bw) {
   return PllCfg{freq, fs, scale, adj, bw * 2.666, bw * bw * 3.555};   // model/fmPll.py:7-10
@@ -153,6 +163,12 @@ int rx_finalize(sdr_rx* r) {
   for (int f = 0; f < SDR_RX_NFILTERS; ++f)
     if (filter_used(r, f) && r->taps[f].empty())
       return fail(SDR_EINVAL, "sdr_rx: the %s filter taps are not set", kFilter[f].name);
+  if (r->bl_nfft) {                    // (the setters after sdr_rx_set_blend may have undone what it checked)
+    if (!r->de_on) return fail(SDR_EINVAL, "sdr_rx_set_blend: the audio output stage is off (sdr_rx_set_deemph)");
+    if (ceil_div(r->B, r->rf_decim) < r->bl_nfft)
+      return fail(SDR_EINVAL, "sdr_rx_set_blend: nfft %d > %lld demod samples per block", r->bl_nfft,
+                  (long long)ceil_div(r->B, r->rf_decim));
+  }
   RxGeom g{r->S, r->B, r->rf_decim, r->audio_decim, r->rds_up, r->rds_down, r->flags, r->de_on, r->pipe ? r->nq : 1, {}, 0};
   for (int f = 0; f < SDR_RX_NFILTERS; ++f) g.taps[f] = (int64_t)r->taps[f].size();
   g.pllw_bytes = sdr_pll_work_bytes(2, r->S, g.M());
@@ -186,6 +202,12 @@ int rx_finalize(sdr_rx* r) {
     at(r->de_mem, L.reg[DE_STATE], &r->de_state); at(r->de_mem, L.reg[DE_MONO], &r->de_mono);
     for (int q = 0; q < g.nsets; ++q) at(r->de_mem, L.pcm_rg[q], &r->pcms[q]);
     r->pcm = r->pcms[0];
+  }
+  if (r->bl_nfft) {
+    TRY(sdr_rspec_create(r->c, r->S, r->bl_nfft, nullptr, r->bl_nfft / 2, 0, &r->bl_spec));
+    TRY(sdr_blend_create(r->c, r->S, &r->bl_prm, &r->bl));
+    TRY(sdr_blend_gains_dev(r->bl, &r->bl_gains));
+    HIP_TRY(hipMalloc(&r->bl_power, sizeof(float) * (size_t)r->S * (size_t)(r->bl_nfft / 2 + 1)));
   }
   r->plan = rx_plan(r);
   r->ready = true;
@@ -222,7 +244,9 @@ void sdr_rx_destroy(sdr_rx* r) {
     if (r->mid) (void)hipStreamSynchronize(r->mid);
     (void)hipStreamSynchronize(r->c->stream);
   }
-  for (void* p : {r->mem, (void*)r->ctaps, r->de_mem})
+  sdr_rspec_destroy(r->bl_spec);
+  sdr_blend_destroy(r->bl);
+  for (void* p : {r->mem, (void*)r->ctaps, r->de_mem, (void*)r->bl_power})
     if (p) (void)hipFree(p);
   for (void* p : {r->pin_in, (void*)r->pin_out})
     if (p) (void)hipHostFree(p);
@@ -276,6 +300,7 @@ int sdr_rx_reset(sdr_rx* r) {
   HIP_TRY(hipMemcpyAsync(r->pll_state[0], ps.data(), sizeof(double) * ps.size(), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(r->pll_state[1], ps.data(), sizeof(double) * ps.size(), hipMemcpyHostToDevice, st));
   if (r->de_state) HIP_TRY(hipMemsetAsync(r->de_state, 0, (size_t)r->de_reset.bytes, st));
+  if (r->bl) TRY(sdr_blend_reset(r->bl));
   HIP_TRY(hipStreamSynchronize(st));
   r->parity = 0; r->blocks = 0;
   r->last_fs = nullptr; r->host_done = -1;
@@ -297,6 +322,33 @@ int sdr_rx_set_deemph(sdr_rx* r, const double* b, double a1) {
   r->de_b[0] = b[0]; r->de_b[1] = b[1]; r->de_a1 = a1;
   r->de_on = true;
   return SDR_OK;
+}
+
+int sdr_rx_set_blend(sdr_rx* r, const sdr_blend_params* params, int nfft) {
+  CHECK_RX(r);
+  TRY(still_open(r, "sdr_rx_set_blend"));
+  if (nfft == 0) {
+    r->bl_nfft = 0;
+    return SDR_OK;
+  }
+  if (!group_on(r->flags, G_AUDIO)) return fail(SDR_EINVAL, "sdr_rx_set_blend: flags 0x%x produce no audio", r->flags);
+  if (!r->de_on) return fail(SDR_EINVAL, "sdr_rx_set_blend: the audio output stage is off (sdr_rx_set_deemph)");
+  if (nfft < 512 || nfft > SDR_SPEC_MAX_NFFT || (nfft & (nfft - 1)) != 0)
+    return fail(SDR_EINVAL, "sdr_rx_set_blend: nfft=%d must be a power of two in [512, %d]", nfft, SDR_SPEC_MAX_NFFT);
+  const int64_t M = ceil_div(r->B, r->rf_decim);
+  if (M < nfft) return fail(SDR_EINVAL, "sdr_rx_set_blend: nfft %d > %lld demod samples per block", nfft, (long long)M);
+  bool mute_on;
+  TRY(blend_params(params, &r->bl_prm, &mute_on, "sdr_rx_set_blend"));   // sdr_blend_create's rules, before any device work
+  r->bl_nfft = nfft;
+  return SDR_OK;
+}
+
+int sdr_rx_blend_state(sdr_rx* r, double* host) {
+  CHECK_RX(r);
+  if (!r->bl_nfft) return fail(SDR_EINVAL, "sdr_rx_blend_state: the blend is off (sdr_rx_set_blend)");
+  if (host == nullptr) return fail(SDR_EINVAL, "sdr_rx_blend_state: host is NULL");
+  if (!r->ready) TRY(rx_finalize(r));
+  return sdr_blend_state(r->bl, host);
 }
 
 int sdr_rx_pcm(sdr_rx* r, int16_t** dev, int64_t* stride, int64_t* n) {
@@ -605,9 +657,18 @@ int rx_back(RxBlock& b) {
   if (r->de_on) {
     const bool stx = pl.stx;
     const int64_t as = r->out_stride[SDR_RX_O_AUDIO];
-    TRY(sdr_audio_out_dev(r->c, o[stx ? SDR_RX_O_LEFT : SDR_RX_O_AUDIO], stx ? o[SDR_RX_O_RIGHT] : nullptr, r->A, as, S,
-                          r->de_b, r->de_a1, r->de_state, o[stx ? SDR_RX_O_LEFT_DE : SDR_RX_O_AUDIO_DE],
-                          stx ? o[SDR_RX_O_RIGHT_DE] : nullptr, r->pcms[b.q], r->pcm_stride));
+    const float *xl = o[stx ? SDR_RX_O_LEFT : SDR_RX_O_AUDIO], *xr = stx ? o[SDR_RX_O_RIGHT] : nullptr;
+    float *yl = o[stx ? SDR_RX_O_LEFT_DE : SDR_RX_O_AUDIO_DE], *yr = stx ? o[SDR_RX_O_RIGHT_DE] : nullptr;
+    if (r->bl) {
+      // this block's multiplex spectra -> its quality and gains -> the tail ramps to them
+      const int nb = r->bl_nfft / 2 + 1;
+      TRY(sdr_rspec_process_dev(r->bl_spec, o[SDR_RX_O_DEMOD], r->M, r->out_stride[SDR_RX_O_DEMOD], r->bl_power, nb));
+      TRY(sdr_blend_update_dev(r->bl, r->bl_power, nb, nb, kMpxFs));
+      TRY(sdr_audio_blend_dev(r->c, xl, xr, r->A, as, S, r->de_b, r->de_a1, r->de_state, yl, yr, r->pcms[b.q], r->pcm_stride,
+                              r->bl_gains));
+    } else {
+      TRY(sdr_audio_out_dev(r->c, xl, xr, r->A, as, S, r->de_b, r->de_a1, r->de_state, yl, yr, r->pcms[b.q], r->pcm_stride));
+    }
     if (b.de_mono)
       TRY(sdr_iir1_dev(r->c, o[SDR_RX_O_AUDIO], r->A, as, S, r->de_b, r->de_a1, r->de_mono, r->de_mono,
                        o[SDR_RX_O_AUDIO_DE], as));

@@ -96,6 +96,10 @@ int get_iir_tab(sdr_ctx* c, double a1, const double** out);
 // filter.  `what` names the entry point in error messages.
 int run_iir1(sdr_ctx* c, IirLaunch& a, const double* b, double a1, const char* what);
 
+// sdr_blend_params' rules (include/sdr.h): *out = the parameters with NULL's defaults filled in,
+// *mute_on = both mute limits finite; `what` names the entry point in error messages
+int blend_params(const sdr_blend_params* params, sdr_blend_params* out, bool* mute_on, const char* what);
+
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 constexpr double two_pi = 6.283185307179586476925286766559;

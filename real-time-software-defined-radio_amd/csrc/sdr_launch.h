@@ -161,9 +161,36 @@ struct IirLaunch {
   double* agg; double* carry;  // rows of more than one tile: nstreams * nch * sdr_iir1_tiles(n) doubles each
   // set by the launcher
   int64_t ntiles, K; double q[6]; int vec_x, vec_y, vec_pcm;
+  // nullable (last, so that the fields above keep their kernel-argument offsets): device
+  // [nstreams][4] doubles {g0, g1, m0, m1}, the stereo-blend and mute gains at the block's start
+  // and end (blend.hip writes them).  The BLEND instantiations form every sample where they load it:
+  //   t = (i + 1) / n, g = g0 + (g1 - g0) t, m = m0 + (m1 - m0) t
+  //   L' = (float)(m ((L + R) / 2 + g (L - R) / 2)),  R' = (float)(m ((L + R) / 2 - g (L - R) / 2))
+  // in f64 (nch == 1: L' = (float)(m L)), and that f32 is what is filtered, written and converted.
+  const double* gains;
 };
 // tab[k] = (-a1)^(SDR_IIR_ITEMS k), k = 0 .. SDR_IIR_THREADS (host, f64 pow)
 void sdr_iir1_table(double a1, double* tab);
 int64_t sdr_iir1_tiles(int64_t n);
 // reduce -> carry -> apply (rows of one tile, or filter == 0: apply alone)
 hipError_t sdr_launch_iir1(const IirLaunch& a, hipStream_t st);
+
+// Quality and gain control (blend.hip): per stream s the row power + s * stride (nbins one-sided
+// power bins, sdr_rspec's) -> its pilot / RDS ratios and noise floor, the gain targets and the
+// smoothed gains, into state[s][SDR_BLEND_NSTATE] = {pilot_db, rds_db, noise_floor, g_prev, g,
+// m_prev, m, n_updates} and gains[s][4] = {g_prev, g, m_prev, m} (IirLaunch::gains).  band /
+// guard: bin ranges [first, end); guard[b]: up to two ranges of at most SDR_BLEND_MAX_GUARD bins
+// together (0 pilot, 1 RDS).
+#define SDR_BLEND_NSTATE 8
+#define SDR_BLEND_MAX_GUARD 1024
+struct BlendBands { int band[2][2]; int guard[2][2][2]; };
+struct BlendLaunch {
+  const float* power; int64_t stride; int nstreams; BlendBands bd;
+  double blend_lo, blend_hi, mute_lo, mute_hi, attack, release; int mute;
+  double* state; double* gains;
+};
+// mpx_quality's bands for nbins = nfft / 2 + 1 bins at fs (host); false: a band is empty or a
+// guard holds more than SDR_BLEND_MAX_GUARD bins
+bool sdr_blend_bands(double fs, int nbins, BlendBands* out);
+hipError_t sdr_launch_blend_update(const BlendLaunch& a, hipStream_t st);
+hipError_t sdr_launch_blend_reset(double* state, double* gains, int nstreams, int mute, hipStream_t st);

@@ -200,6 +200,30 @@ def audio_out(left, right=None, *, b=None, a=None, state=None, rows=True, pcm=Tr
             buf.free()
 
 
+def audio_blend_dev(left_ptr, right_ptr, n, stride, nstreams, gains_ptr, *, b=None, a=None, state_ptr=None,
+                    left_out_ptr=None, right_out_ptr=None, pcm_ptr=None, pcm_stride=None, ctx=None):
+    """The audio output stage with a gain ramp, on device rows (sdr_audio_blend_dev; async on the
+    context stream): nstreams rows of n f32 at left_ptr / right_ptr (right_ptr None: mono), `stride`
+    floats apart; gains_ptr: device [nstreams][4] float64 {g0, g1, m0, m1} (BlendControl.gains_ptr).
+    Sample i becomes, in f64 and rounded once to f32, with t = (i + 1) / n, g = g0 + (g1 - g0) t,
+    m = m0 + (m1 - m0) t:  L' = m ((L + R) / 2 + g (L - R) / 2),  R' = m ((L + R) / 2 - g (L - R) / 2)
+    (mono: L' = m L); that f32 goes through the section b, a (None: no filter; state_ptr: device
+    [nstreams][2] float64, in and out) into the f32 rows at left_out_ptr / right_out_ptr and the
+    interleaved int16 PCM at pcm_ptr (pcm_stride int16 apart, default 2 n), as audio_out's."""
+    n, stride, nstreams = int(n), int(stride), int(nstreams)
+    if not gains_ptr:
+        raise ValueError("gains_ptr is NULL")
+    if n < 1 or nstreams < 1 or stride < n:
+        raise ValueError(f"n={n}, nstreams={nstreams} must be >= 1 and stride={stride} >= n")
+    bb, a1 = (None, 0.0) if b is None else _section(b, 1.0 if a is None else a)
+    if bb is not None and not state_ptr:
+        raise ValueError("a filter needs its state")
+    pcm_stride = 2 * n if pcm_stride is None else int(pcm_stride)
+    c = _ctx(ctx)
+    check(c.lib.sdr_audio_blend_dev(c.handle, left_ptr, right_ptr, n, stride, nstreams, f64p(bb), a1, state_ptr,
+                                    left_out_ptr, right_out_ptr, pcm_ptr, pcm_stride, gains_ptr), "sdr_audio_blend_dev")
+
+
 def fmDemodArctan(I, Q, prev_phase=0.0, ctx=None):
     """(fm_demod, prev_phase) of model/fmSupportLib.py:15-44 (atan2 + np.unwrap step)."""
     I = c_f32(_check_x(I))
