@@ -720,6 +720,50 @@ int sdr_rds_links_events(sdr_rds_links* links, int64_t* ev, int64_t* n_events, i
 int sdr_rds_links_bits(sdr_rds_links* links, int stream, uint8_t* bits, int64_t max_bits, int64_t* n_bits,
                        uint8_t* diff, int64_t max_diff, int64_t* n_diff);
 
+/* ---- RDS block synchronisation on the device, for all streams of a call -----------------
+ * What a tuner does with the differential bits, where the link layer's frame rule stops at the
+ * first damaged block: acquisition, a flywheel, the (26, 16) code's burst correction, offset C'.
+ * The host model rdssync.py RdsBlockSync is the specification; records, state and counters equal
+ * it after every call, whatever the split of a stream into calls (csrc/rds_sync.hip, two
+ * launches per call).  Window p is D[p .. p + 25] of the stream's bits since reset, so positions
+ * compare with sdr_rds_links event positions.  Slots: A 0, B 1, C and C' 2, D 3.
+ *   SEARCH from s0 (0 after reset): the first p with p - 26 >= s0 whose window and the window
+ *     26 bits before it have offset syndromes in consecutive slots gives two status-0 records
+ *     and SYNC with the next block at p + 26.
+ *   SYNC: the block of the expected slot every 26 bits: status 0 error-free, 1 corrected (an
+ *     error pattern whose first and last flipped bits are at most max_burst - 1 apart), 2
+ *     uncorrectable.  In slot 2 an exact C or C' syndrome decides the type; otherwise the version
+ *     bit (bit 11) of the B word 26 bits before does, if that record is of this sync run and of
+ *     status <= 1 (else status 2, type C).  bad_run counts blocks in a row that were not
+ *     error-free; when it reaches lose_after the block's record is still emitted and SEARCH
+ *     resumes with s0 behind it.
+ * sdr_rds_sync_set_params: max_burst 0 .. SDR_RDS_SYNC_MAX_BURST (default 2), lose_after
+ *   1 .. 255 (default 12); the host builds the 1024-entry syndrome table (synchronises).
+ * sdr_rds_sync_process_dev: async on the context stream, nothing is read back.  Row s is the n
+ *   bytes at bits + s * stride, only bit 0 of each counts; 0 <= n <= max_bits, stride >= n.
+ *   counts_dev: NULL (every stream takes n bits) or a device array of per-stream counts 0 .. n.
+ * sdr_rds_sync_process_links: every stream takes exactly the scanned bits the link bank's last
+ *   call added (none where that call faulted); call it once after each link call.  Same context
+ *   and stream count; max_bits must cover what a link call of the bank's max_n can add.
+ * sdr_rds_sync_blocks (synchronises): the last call's records, rec[nstreams][max_records][4] =
+ *   {type 0..3 = A..D or 4 = C', position, status, word after correction (as received for status
+ *   2)}, max_records = max_bits / 26 + 3 (no call can give more), n_rec[s] of them valid.
+ * sdr_rds_sync_state (synchronises): per stream synced[s], next_pos[s] (SYNC: the next block;
+ *   SEARCH: s0) and counters[s][5] = blocks of status 0 / 1 / 2, acquisitions, losses since
+ *   reset.  Any pointer may be NULL. */
+#define SDR_RDS_SYNC_MAX_STREAMS 65535
+#define SDR_RDS_SYNC_MAX_BITS (1 << 24)
+#define SDR_RDS_SYNC_MAX_BURST 5
+typedef struct sdr_rds_sync sdr_rds_sync;
+int sdr_rds_sync_create(sdr_ctx* ctx, int nstreams, int64_t max_bits, sdr_rds_sync** out);
+void sdr_rds_sync_destroy(sdr_rds_sync* sync);
+int sdr_rds_sync_reset(sdr_rds_sync* sync);
+int sdr_rds_sync_set_params(sdr_rds_sync* sync, int max_burst, int lose_after);
+int sdr_rds_sync_process_dev(sdr_rds_sync* sync, const uint8_t* bits, int64_t n, int64_t stride, const int32_t* counts_dev);
+int sdr_rds_sync_process_links(sdr_rds_sync* sync, sdr_rds_links* links);
+int sdr_rds_sync_blocks(sdr_rds_sync* sync, int64_t* rec, int64_t* n_rec);
+int sdr_rds_sync_state(sdr_rds_sync* sync, int32_t* synced, int64_t* next_pos, int64_t* counters);
+
 #ifdef __cplusplus
 }
 #endif

@@ -169,6 +169,14 @@ SIGNATURES = {
     "sdr_rds_links_process_dev": (_i32, [_vp, _vp, _i64, _i64]),
     "sdr_rds_links_events": (_i32, [_vp, _vp, _vp, _vp]),
     "sdr_rds_links_bits": (_i32, [_vp, _i32, _vp, _i64, _c.POINTER(_i64), _vp, _i64, _c.POINTER(_i64)]),
+    "sdr_rds_sync_create": (_i32, [_vp, _i32, _i64, _c.POINTER(_vp)]),
+    "sdr_rds_sync_destroy": (None, [_vp]),
+    "sdr_rds_sync_reset": (_i32, [_vp]),
+    "sdr_rds_sync_set_params": (_i32, [_vp, _i32, _i32]),
+    "sdr_rds_sync_process_dev": (_i32, [_vp, _vp, _i64, _i64, _vp]),
+    "sdr_rds_sync_process_links": (_i32, [_vp, _vp]),
+    "sdr_rds_sync_blocks": (_i32, [_vp, _vp, _vp]),
+    "sdr_rds_sync_state": (_i32, [_vp, _vp, _vp, _vp]),
 }
 
 _lib = None

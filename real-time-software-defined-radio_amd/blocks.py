@@ -603,6 +603,76 @@ class RdsLinkBank(_Handle):
         """Every stream back to block 0."""
         check(self.lib.sdr_rds_links_reset(self.handle), "sdr_rds_links_reset")
 
+    def block_sync(self, **kw) -> "RdsSyncBank":
+        """A device-side block synchroniser sized to this bank (RdsSyncBank: one stream per link
+        stream, max_bits what one link call can add); feed it with sync.process_links(bank)
+        after each link call."""
+        kw.setdefault("ctx", self.ctx)
+        return RdsSyncBank(self.S, -(-self.max_n // 24) // 2, **kw)
+
+
+class RdsSyncBank(_Handle):
+    """RDS block synchronisation for `nstreams` streams at once, on the GPU (sdr_rds_sync,
+    csrc/rds_sync.hip): acquisition, flywheel, burst correction and offset C' over every stream's
+    differential bits, all state in device memory.  rdssync.RdsBlockSync is the specification:
+    records, state and counters equal it after every call, whatever the split.
+
+    max_bits: the most bits a call may bring per stream.  max_burst, lose_after: as
+    RdsBlockSync's.  blocks() returns the last call's records, per stream a list of
+    (type, position, status, word) -- what RdsProgramme.feed takes."""
+
+    TYPES = ("A", "B", "C", "D", "C'")
+    _prefix = "sdr_rds_sync"
+
+    def __init__(self, nstreams: int, max_bits: int, max_burst: int = 2, lose_after: int = 12, ctx=None):
+        self.S, self.max_bits = int(nstreams), int(max_bits)
+        self.max_records = self.max_bits // 26 + 3
+        self.ctx = ctx if ctx is not None else _lib.get_context()
+        self.lib = self.ctx.lib
+        h = ctypes.c_void_p()
+        check(self.lib.sdr_rds_sync_create(self.ctx.handle, self.S, self.max_bits, ctypes.byref(h)), "sdr_rds_sync_create")
+        self.handle = h
+        try:
+            self.set_params(max_burst, lose_after)
+        except Exception:
+            self.close()
+            raise
+
+    def set_params(self, max_burst: int, lose_after: int):
+        self._do("set_params", int(max_burst), int(lose_after))
+        self.max_burst, self.lose_after = int(max_burst), int(lose_after)
+
+    def process_dev(self, ptr: int, n: int, stride: int, counts_ptr: int = 0):
+        """One call for every stream: row s is the n bytes at device pointer ptr + s stride, bit 0
+        of each byte a bit.  counts_ptr: 0 (every stream takes n bits) or a device array of
+        nstreams int32 counts 0 .. n.  Async on the context stream."""
+        self._do("process_dev", ptr, int(n), int(stride), counts_ptr or None)
+
+    def process_links(self, bank: "RdsLinkBank"):
+        """Every stream takes the scanned bits the link bank's last call added (none where it
+        faulted).  Async on the context stream; call it once after each link call."""
+        self._do("process_links", bank.handle)
+
+    def blocks(self):
+        """The last call's records, after waiting for it: per stream a list of 4-tuples."""
+        rec = np.zeros((self.S, self.max_records, 4), dtype=np.int64)
+        nr = np.zeros(self.S, dtype=np.int64)
+        self._do("blocks", rec.ctypes.data, nr.ctypes.data)
+        return [[tuple(r) for r in rec[s, :min(int(nr[s]), self.max_records)].tolist()] for s in range(self.S)]
+
+    def state(self):
+        """Per stream (synced, next position, blocks of status 0, 1, 2, acquisitions, losses) --
+        RdsBlockSync.state() -- after waiting for the last call."""
+        synced = np.zeros(self.S, dtype=np.int32)
+        pos = np.zeros(self.S, dtype=np.int64)
+        cnt = np.zeros((self.S, 5), dtype=np.int64)
+        self._do("state", synced.ctypes.data, pos.ctypes.data, cnt.ctypes.data)
+        return [(int(synced[s]), int(pos[s]), *(int(v) for v in cnt[s])) for s in range(self.S)]
+
+    def reset(self):
+        """Every stream back to SEARCH at position 0; the counters to 0."""
+        self._do("reset")
+
 
 def rds_groups(events):
     """One stream's events -> the groups in them: an accepted A at position p with accepted B, C,

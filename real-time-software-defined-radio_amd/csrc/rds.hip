@@ -25,6 +25,7 @@
 
 #include <new>
 
+#include "rds_links.h"
 #include "sdr_ctx.h"
 
 using namespace sdrint;
@@ -89,6 +90,7 @@ struct RdsArgs {
   int* tcount; uint32_t* rec; int64_t tiles_stride;   // per tile: matches, and their records in the tile's slots
   uint2* cm;                                // the stream's matches in window order: {window, type << 16 | word}
   int* nbd;                                 // [stream][2]: the last call's bit and scanned-bit counts
+  int* added;                               // [stream][2]: {C, L - C}, the scanned bits the last call added
   int64_t* ev; int64_t* nev; int* status; int64_t max_events;
   int resync;
 };
@@ -303,6 +305,8 @@ __global__ __launch_bounds__(RDS_T) void rds_frame_kernel(const RdsArgs a) {
       a.nev[s] = 0;
       a.nbd[2 * s] = 0;
       a.nbd[2 * s + 1] = 0;
+      a.added[2 * s] = 0;
+      a.added[2 * s + 1] = 0;
     }
   }
   if (fault) return;
@@ -424,6 +428,8 @@ __global__ __launch_bounds__(RDS_T) void rds_frame_kernel(const RdsArgs a) {
     a.status[s] = ne > a.max_events ? SDR_RDS_LINKS_OVERFLOW : 0;
     a.nbd[2 * s] = p.nb;
     a.nbd[2 * s + 1] = p.L;
+    a.added[2 * s] = p.C;
+    a.added[2 * s + 1] = p.L - p.C;
   }
 }
 
@@ -443,6 +449,7 @@ struct sdr_rds_links {
   uint32_t* rec = nullptr;
   uint2* cm = nullptr;
   int* nbd = nullptr;
+  int* added = nullptr;
   int64_t* ev = nullptr;
   int64_t* nev = nullptr;
   int* status = nullptr;
@@ -459,12 +466,18 @@ int clear_outputs(sdr_rds_links* l) {
   HIP_TRY(hipMemsetAsync(l->state, 0, sizeof(RdsState) * l->S, st));
   HIP_TRY(hipMemsetAsync(l->cnt, 0, sizeof(unsigned) * 2 * l->S, st));
   HIP_TRY(hipMemsetAsync(l->nbd, 0, sizeof(int) * 2 * l->S, st));
+  HIP_TRY(hipMemsetAsync(l->added, 0, sizeof(int) * 2 * l->S, st));
   HIP_TRY(hipMemsetAsync(l->nev, 0, sizeof(int64_t) * l->S, st));
   HIP_TRY(hipMemsetAsync(l->status, 0, sizeof(int) * l->S, st));
   return SDR_OK;
 }
 
 }  // namespace
+
+// what the block sync stage (rds_sync.hip) reads of a link bank
+sdrint::RdsLinksView sdrint::rds_links_view(const sdr_rds_links* l) {
+  return RdsLinksView{l->ctx, l->S, max_scanned(l->max_n) - 27, l->diff, l->diff_stride, l->added};
+}
 
 extern "C" {
 
@@ -501,6 +514,7 @@ int sdr_rds_links_create(sdr_ctx* c, int nstreams, int64_t max_n, int64_t max_ev
   if (e == hipSuccess) e = hipMalloc(&l->rec, sizeof(uint32_t) * S * l->tiles_stride * RDS_TILE);
   if (e == hipSuccess) e = hipMalloc(&l->cm, sizeof(uint2) * S * l->tiles_stride * RDS_TILE);
   if (e == hipSuccess) e = hipMalloc(&l->nbd, sizeof(int) * 2 * S);
+  if (e == hipSuccess) e = hipMalloc(&l->added, sizeof(int) * 2 * S);
   if (e == hipSuccess) e = hipMalloc(&l->ev, sizeof(int64_t) * 4 * S * (size_t)max_events);
   if (e == hipSuccess) e = hipMalloc(&l->nev, sizeof(int64_t) * S);
   if (e == hipSuccess) e = hipMalloc(&l->status, sizeof(int) * S);
@@ -529,6 +543,7 @@ void sdr_rds_links_destroy(sdr_rds_links* l) {
   (void)hipFree(l->rec);
   (void)hipFree(l->cm);
   (void)hipFree(l->nbd);
+  (void)hipFree(l->added);
   (void)hipFree(l->ev);
   (void)hipFree(l->nev);
   (void)hipFree(l->status);
@@ -574,6 +589,7 @@ int sdr_rds_links_process_dev(sdr_rds_links* l, const float* rrc_i, int64_t n, i
   a.cm = l->cm;
   a.tiles_stride = l->tiles_stride;
   a.nbd = l->nbd;
+  a.added = l->added;
   a.ev = l->ev;
   a.nev = l->nev;
   a.status = l->status;

@@ -18,7 +18,7 @@ FS = 2.4e6
 # RDS block coding (IEC 62106): 26-bit blocks = 16 information bits + 10-bit checkword,
 # checkword = (m(x) x^10 mod g(x)) XOR offset word; g(x) = x^10+x^8+x^7+x^5+x^4+x^3+1.
 RDS_POLY = 0x5B9
-RDS_OFFSETS = {"A": 0x0FC, "B": 0x198, "C": 0x168, "D": 0x1B4}
+RDS_OFFSETS = {"A": 0x0FC, "B": 0x198, "C": 0x168, "D": 0x1B4, "C'": 0x350}
 
 
 def rds_block_bits(info: int, offset: str) -> list:
@@ -46,6 +46,44 @@ def rds_symbols(nbits: int, seed: int = 0) -> np.ndarray:
         e ^= bits[t]
         sym[2 * t], sym[2 * t + 1] = (1.0, -1.0) if e else (-1.0, 1.0)
     return sym
+
+
+def rds_group_bits(groups) -> list:
+    """The differential-layer bits of a list of groups (a, b, c, d), 104 bits each: blocks A, B,
+    C or -- where b's version bit (bit 11) is set -- C', and D."""
+    bits = []
+    for a, b, c, d in groups:
+        bits += rds_block_bits(a, "A") + rds_block_bits(b, "B")
+        bits += rds_block_bits(c, "C'" if (b >> 11) & 1 else "C") + rds_block_bits(d, "D")
+    return bits
+
+
+def rds_ps_groups(pi: int, name: str, version_b: bool = False, pty: int = 0, tp: int = 0) -> list:
+    """The four type-0 groups (0A, or 0B with the PI repeated in block C') of an eight-character
+    programme service name."""
+    name = name.ljust(8)[:8].encode("ascii")
+    head = (int(version_b) << 11) | ((tp & 1) << 10) | ((pty & 31) << 5)
+    return [(pi, head | seg, pi if version_b else 0xE0CD, (name[2 * seg] << 8) | name[2 * seg + 1])
+            for seg in range(4)]
+
+
+def rds_rt_groups(pi: int, text: str, flag: int = 0, version_b: bool = False, pty: int = 0, tp: int = 0) -> list:
+    """The type-2 groups of a radiotext (2A: four characters a group, up to 64; 2B: two, up to
+    32), ended by 0x0D where it is shorter than that."""
+    per = 2 if version_b else 4
+    raw = text.encode("ascii")[:16 * per]
+    if len(raw) < 16 * per:
+        raw += b"\r"
+    raw += b" " * (-len(raw) % per)
+    head = (2 << 12) | (int(version_b) << 11) | ((tp & 1) << 10) | ((pty & 31) << 5) | ((flag & 1) << 4)
+    out = []
+    for seg in range(len(raw) // per):
+        ch = raw[per * seg:per * seg + per]
+        if version_b:
+            out.append((pi, head | seg, pi, (ch[0] << 8) | ch[1]))
+        else:
+            out.append((pi, head | seg, (ch[0] << 8) | ch[1], (ch[2] << 8) | ch[3]))
+    return out
 
 
 def fm_iq(n_complex: int, seed: int = 0, fs: float = FS, snr_db: float = 30.0, chunk: int = 1 << 22,
