@@ -764,6 +764,53 @@ int sdr_rds_sync_process_links(sdr_rds_sync* sync, sdr_rds_links* links);
 int sdr_rds_sync_blocks(sdr_rds_sync* sync, int64_t* rec, int64_t* n_rec);
 int sdr_rds_sync_state(sdr_rds_sync* sync, int32_t* synced, int64_t* next_pos, int64_t* counters);
 
+/* ---- RDS symbol clock recovery on the device, for all streams of a call ------------------
+ * The in-phase RRC rows (24 samples a symbol) -> differential bits, byte per bit, with an int32
+ * count per stream, left in device memory for sdr_rds_sync_process_dev.  Where the link layer
+ * fixes its sampling offset on the first 24 samples for ever, this stage follows the symbol clock.
+ * The host model rdsclock.py RdsSymbolClock is the specification; bits, counts and state equal it
+ * after every call, whatever the split of a stream into calls (csrc/rds_clock.hip, six launches
+ * per call).  A stream is cut into segments of 768 samples (32 symbols) on its absolute sample
+ * grid; only complete segments are worked on, the rest is carried.
+ *   Energy: E_g[p] = sum of x[768 g + 24 j + p]^2 over j = 0 .. 31 ascending, in f64, a
+ *     non-finite sample counting as 0; A_g = the E of the last min(window, g + 1) segments, oldest
+ *     first; phat_g = the first maximum of A_g.
+ *   Tracking: phi_0 = phat_0; later phi moves one sample (mod 24) towards phat_g when they are 2
+ *     or more apart.  Segment g gives the samples x[768 g + 24 j + phi_g], j = j0 .. 31, j0 = 0
+ *     but 1 when phi stepped 23 -> 0 and -1 when it stepped 0 -> 23: instants 23 .. 25 apart.
+ *   Pairing: over the symbol pairs (m, m + 1) whose second symbol lies in the last
+ *     min(window, g + 1) segments, C0 / C1 count those with even / odd m whose samples differ in
+ *     (x > 0).  Segment 0 sets pi = 0 if C0 >= C1 else 1; later pi moves when the other count
+ *     leads by more than `hysteresis`.  A pair with m = pi (mod 2) whose first symbol no pair has
+ *     used gives bit = x[m] > x[m + 1]; diff = bit xor the bit before it (the first gives none).
+ * sdr_rds_clock_set_params: window 1 .. SDR_RDS_CLOCK_MAX_WINDOW (default 4), hysteresis
+ *   0 .. SDR_RDS_CLOCK_MAX_HYSTERESIS (default 8); they hold for the calls that follow.
+ * sdr_rds_clock_process_dev: async on the context stream, nothing is read back.  Row s is the n
+ *   floats at rrc_i + s * stride, at any 4-byte alignment; 0 <= n <= max_n, stride >= n; nothing
+ *   beyond n is read.
+ * sdr_rds_clock_bits: the rows the next stage reads: row s is the bytes at *dev + s * *stride,
+ *   (*counts_dev)[s] of them valid after a call, at most *max_bits = 17 ceil(max_n / 768) + 1:
+ *   sdr_rds_sync_process_dev(sync, *dev, *max_bits, *stride, *counts_dev).  Any pointer may be NULL.
+ * sdr_rds_clock_fetch (synchronises): the last call's bits[nstreams][max_bits] and counts[nstreams]
+ *   to the host; either may be NULL.
+ * sdr_rds_clock_state (synchronises): state[nstreams][SDR_RDS_CLOCK_NSTATE] = consumed samples,
+ *   segments, phi, pi, symbols, Manchester bits (one more than the differential bits), steps
+ *   forward, steps back, wraps, pairing changes since reset. */
+#define SDR_RDS_CLOCK_MAX_STREAMS 65535
+#define SDR_RDS_CLOCK_MAX_N (1 << 24)
+#define SDR_RDS_CLOCK_MAX_WINDOW 16
+#define SDR_RDS_CLOCK_MAX_HYSTERESIS (1 << 20)
+#define SDR_RDS_CLOCK_NSTATE 10
+typedef struct sdr_rds_clock sdr_rds_clock;
+int sdr_rds_clock_create(sdr_ctx* ctx, int nstreams, int64_t max_n, sdr_rds_clock** out);
+void sdr_rds_clock_destroy(sdr_rds_clock* clk);
+int sdr_rds_clock_reset(sdr_rds_clock* clk);
+int sdr_rds_clock_set_params(sdr_rds_clock* clk, int window, int hysteresis);
+int sdr_rds_clock_process_dev(sdr_rds_clock* clk, const float* rrc_i, int64_t n, int64_t stride);
+int sdr_rds_clock_bits(sdr_rds_clock* clk, uint8_t** dev, int64_t* stride, int32_t** counts_dev, int64_t* max_bits);
+int sdr_rds_clock_fetch(sdr_rds_clock* clk, uint8_t* bits, int32_t* counts);
+int sdr_rds_clock_state(sdr_rds_clock* clk, int64_t* state);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,7 @@ RX_STAGES = ("fe", "filters_of_demod", "rds_square", "pll", "mix_lpf", "resample
 # PLL solve counters (include/sdr.h SDR_PLL_ST_*)
 # device-side RDS link layer (include/sdr.h sdr_rds_links_*)
 SDR_RDS_LINKS_MIN_N, SDR_RDS_LINKS_FAULT, SDR_RDS_LINKS_OVERFLOW = 1536, 1, 2
+SDR_RDS_CLOCK_NSTATE = 10
 PLL_STATS = ("recurrences", "spec_r0", "spec_r1", "spec_r2", "sequential", "long_guessed", "long_chained",
              "long_maxgap", "long_stops", "long_tail", "long_linear")
 
@@ -177,6 +178,14 @@ SIGNATURES = {
     "sdr_rds_sync_process_links": (_i32, [_vp, _vp]),
     "sdr_rds_sync_blocks": (_i32, [_vp, _vp, _vp]),
     "sdr_rds_sync_state": (_i32, [_vp, _vp, _vp, _vp]),
+    "sdr_rds_clock_create": (_i32, [_vp, _i32, _i64, _c.POINTER(_vp)]),
+    "sdr_rds_clock_destroy": (None, [_vp]),
+    "sdr_rds_clock_reset": (_i32, [_vp]),
+    "sdr_rds_clock_set_params": (_i32, [_vp, _i32, _i32]),
+    "sdr_rds_clock_process_dev": (_i32, [_vp, _vp, _i64, _i64]),
+    "sdr_rds_clock_bits": (_i32, [_vp, _c.POINTER(_vp), _c.POINTER(_i64), _c.POINTER(_vp), _c.POINTER(_i64)]),
+    "sdr_rds_clock_fetch": (_i32, [_vp, _vp, _vp]),
+    "sdr_rds_clock_state": (_i32, [_vp, _vp]),
 }
 
 _lib = None

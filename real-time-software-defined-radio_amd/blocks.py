@@ -387,6 +387,15 @@ class Receiver(_Handle):
         kw.setdefault("ctx", self.ctx)
         return RdsLinkBank(self.S, self._length("rrc_i"), **kw)
 
+    def rds_clock(self, **kw) -> "RdsClockBank":
+        """A device-side RDS symbol clock sized to this receiver (RdsClockBank: one stream per
+        receiver stream, rows of the "rrc_i" length); feed it with bank.process_rx(receiver) after
+        each block, and its bits into bank.block_sync() with bank.feed(sync).  Needs rds=True."""
+        if not self.flags & SDR_RX_RDS:
+            raise ValueError("rds_clock needs a receiver with rds=True")
+        kw.setdefault("ctx", self.ctx)
+        return RdsClockBank(self.S, self._length("rrc_i"), **kw)
+
     def mpx_spectrum(self, nfft: int = 1024, hop=None, navg: int = 0, **kw) -> "RowSpectrum":
         """A RowSpectrum sized to this receiver's "demod" rows (one row per stream, the multiplex at
         design.AUDIO_FS; hop defaults to nfft / 2); feed it with spectrum.process_rx(receiver,
@@ -672,6 +681,89 @@ class RdsSyncBank(_Handle):
     def reset(self):
         """Every stream back to SEARCH at position 0; the counters to 0."""
         self._do("reset")
+
+
+class RdsClockBank(_Handle):
+    """RDS symbol clock recovery for `nstreams` streams at once, on the GPU (sdr_rds_clock,
+    csrc/rds_clock.hip): the in-phase RRC rows are read where the receiver left them, and every
+    stream's differential bits (byte per bit) and an int32 count per stream stay in device memory
+    for RdsSyncBank.process_dev -- feed(sync).  Where RdsLinkBank keeps the sampling offset of the
+    first 24 samples for ever, this follows the symbol clock: a receiver whose crystal is off keeps
+    its bits.  rdsclock.RdsSymbolClock is the specification: bits, counts and state equal it
+    after every call, whatever the split.
+
+    max_n: the longest row a call may bring (0 <= n <= max_n).  window, hysteresis: as
+    RdsSymbolClock's.  max_bits: the most bits a call can give per stream."""
+
+    _prefix = "sdr_rds_clock"
+
+    def __init__(self, nstreams: int, max_n: int, window: int = 4, hysteresis: int = 8, ctx=None):
+        self.S, self.max_n = int(nstreams), int(max_n)
+        self.ctx = ctx if ctx is not None else _lib.get_context()
+        self.lib = self.ctx.lib
+        h = ctypes.c_void_p()
+        check(self.lib.sdr_rds_clock_create(self.ctx.handle, self.S, self.max_n, ctypes.byref(h)), "sdr_rds_clock_create")
+        self.handle = h
+        try:
+            self.set_params(window, hysteresis)
+            dev, cnt = ctypes.c_void_p(), ctypes.c_void_p()
+            stride, mb = ctypes.c_int64(), ctypes.c_int64()
+            self._do("bits", ctypes.byref(dev), ctypes.byref(stride), ctypes.byref(cnt), ctypes.byref(mb))
+        except Exception:
+            self.close()
+            raise
+        self.bits_ptr, self.bits_stride, self.counts_ptr, self.max_bits = dev.value, stride.value, cnt.value, mb.value
+
+    def set_params(self, window: int, hysteresis: int):
+        """For the calls that follow (the model takes them at construction: set them before the
+        first call to equal it)."""
+        self._do("set_params", int(window), int(hysteresis))
+        self.window, self.hysteresis = int(window), int(hysteresis)
+
+    def process_dev(self, ptr: int, n: int, stride: int):
+        """One call for every stream: row s is the n floats at device pointer ptr + 4 s stride,
+        0 <= n <= max_n.  Async on the context stream."""
+        self._do("process_dev", ptr, int(n), int(stride))
+
+    def process_rx(self, receiver: "Receiver"):
+        """The receiver's latest "rrc_i" rows (looked up at every call: a pipelined receiver
+        alternates its row sets)."""
+        if receiver.S != self.S:
+            raise ValueError(f"the receiver has {receiver.S} streams, the bank {self.S}")
+        ptr, stride, n = receiver.output_ptr("rrc_i")
+        self.process_dev(ptr, n, stride)
+
+    def bits(self):
+        """The last call's differential bits, after waiting for it: per stream a uint8 array."""
+        b = np.zeros((self.S, self.max_bits), dtype=np.uint8)
+        cnt = np.zeros(self.S, dtype=np.int32)
+        self._do("fetch", b.ctypes.data, cnt.ctypes.data)
+        return [b[s, :int(cnt[s])].copy() for s in range(self.S)]
+
+    def state(self):
+        """Per stream (consumed samples, segments, phi, pi, symbols, bits, steps forward, steps
+        back, wraps, pairing changes) -- RdsSymbolClock.state() -- after waiting for the last call."""
+        st = np.zeros((self.S, _lib.SDR_RDS_CLOCK_NSTATE), dtype=np.int64)
+        self._do("state", st.ctypes.data)
+        return [tuple(int(v) for v in row) for row in st]
+
+    def reset(self):
+        """Every stream back to sample 0; the counters to 0."""
+        self._do("reset")
+
+    def block_sync(self, **kw) -> "RdsSyncBank":
+        """A device-side block synchroniser sized to this bank (RdsSyncBank: one stream per clock
+        stream, max_bits what one call of max_n can add); feed it with bank.feed(sync) after each
+        call."""
+        kw.setdefault("ctx", self.ctx)
+        return RdsSyncBank(self.S, self.max_bits, **kw)
+
+    def feed(self, sync: "RdsSyncBank"):
+        """The last call's bits into the block synchroniser, device to device: every stream takes
+        its own count.  Async on the context stream; call it once after each call."""
+        if sync.S != self.S:
+            raise ValueError(f"the sync has {sync.S} streams, the bank {self.S}")
+        sync.process_dev(self.bits_ptr, self.max_bits, self.bits_stride, self.counts_ptr)
 
 
 def rds_groups(events):
