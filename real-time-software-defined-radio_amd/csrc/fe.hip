@@ -1313,6 +1313,25 @@ hipError_t sdr_launch_fe_mono(const FeLaunch& a, const float* ataps, const float
   return launch_ring_t<101, true>(p, *a.taps, ra, st);
 }
 
+// u8 IQ rows as the f32 samples every front end normalises them to, (u8 - 128) / 128
+// (src/iofunc.cpp:61-69; exact in f32), for the generic kernels, which read f32: one lane per value
+__global__ __launch_bounds__(256) void iq_u8_f32_kernel(const uint8_t* iq, int64_t nv, int64_t stride_v, float* out,
+                                                        int64_t out_stride_v) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int s = blockIdx.y;
+  if (i < nv) out[(int64_t)s * out_stride_v + i] = ((float)iq[(int64_t)s * stride_v + i] - 128.f) / 128.f;
+}
+
+hipError_t sdr_launch_iq_u8_f32(const void* iq, int64_t n, int64_t stride, int nstreams, float* out, int64_t out_stride,
+                                hipStream_t st) {
+  if (n <= 0 || nstreams <= 0) return hipSuccess;
+  const int64_t blocks = (2 * n + 255) / 256;
+  if (blocks > 0x7fffffff) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(iq_u8_f32_kernel, dim3((unsigned)blocks, nstreams), dim3(256), 0, st,
+                     static_cast<const uint8_t*>(iq), 2 * n, 2 * stride, out, 2 * out_stride);
+  return hipGetLastError();
+}
+
 hipError_t sdr_launch_iq_zf(const void* iq, int u8, int64_t n, int64_t stride, int nstreams,
                             const double* b_dev, int T, const double* zi_i, const double* zi_q,
                             int64_t zi_stride, double* zf_i, double* zf_q, hipStream_t st) {

@@ -100,6 +100,7 @@ struct sdr_rx : RxLayout {             // M, A, R, the rows' lengths and strides
   uint64_t keep = ~0ull, keep_now = ~0ull;   // keep_now: this call's (sdr_rx_submit: what it was asked for)
   bool made[SDR_RX_NOUTPUTS] = {};     // what the latest block materialised
   float* ctaps = nullptr;              // the composite RDS taps (rx_cres_kernel), device; null: two-stage path
+  float* iq_f32 = nullptr;             // u8 blocks the tiled FE kernels cannot take, as f32 for the generic ones (rx_front)
   // sdr_rx_set_deemph: the audio output stage (audio.hip) after the combiner, on the context stream
   bool de_on = false;
   double de_b[2] = {}, de_a1 = 0.0;
@@ -246,7 +247,7 @@ void sdr_rx_destroy(sdr_rx* r) {
   }
   sdr_rspec_destroy(r->bl_spec);
   sdr_blend_destroy(r->bl);
-  for (void* p : {r->mem, (void*)r->ctaps, r->de_mem, (void*)r->bl_power})
+  for (void* p : {r->mem, (void*)r->ctaps, (void*)r->iq_f32, r->de_mem, (void*)r->bl_power})
     if (p) (void)hipFree(p);
   for (void* p : {r->pin_in, (void*)r->pin_out})
     if (p) (void)hipHostFree(p);
@@ -473,7 +474,19 @@ int rx_front(RxBlock& b, const void* iq, int64_t xs, bool fast) {
     fst = FeState{iq, r->B, xs, rf->dev_f64, zin(b, Z_FE_I), zin(b, Z_FE_Q), zout(b, Z_FE_I), zout(b, Z_FE_Q),
                   r->zlen[Z_FE_I], r->last_phi, r->wraps, r->phase, Trf, r->u8, 1};
   } else {
-    TRY(sdr_rf_frontend_dev(r->c, iq, r->u8 ? SDR_IQ_U8 : SDR_IQ_F32, r->B, xs, 0, S, r->taps[SDR_RX_F_RF].data(),
+    const void* x = iq;
+    int64_t xst = xs;
+    if (r->u8) {
+      // the generic kernels read f32: the block as the samples a u8 front end normalises it to,
+      // in packed receiver-owned rows (fs is the context stream here, as the generic path's; 64
+      // floats behind the last row: the f32 tiles, which take such rows at 101 / 151 taps and
+      // decimation 10, load whole 16-B chunks)
+      if (r->iq_f32 == nullptr) HIP_TRY(hipMalloc(&r->iq_f32, sizeof(float) * (2 * (size_t)S * (size_t)r->B + 64)));
+      HIP_TRY(sdr_launch_iq_u8_f32(iq, r->B, xs, S, r->iq_f32, r->B, fs));
+      x = r->iq_f32;
+      xst = r->B;
+    }
+    TRY(sdr_rf_frontend_dev(r->c, x, SDR_IQ_F32, r->B, xst, 0, S, r->taps[SDR_RX_F_RF].data(),
                             Trf, r->rf_decim, zin(b, Z_FE_I), zin(b, Z_FE_Q), r->zlen[Z_FE_I], zout(b, Z_FE_I),
                             zout(b, Z_FE_Q), r->phase, b.o[SDR_RX_O_DEMOD], ms, nullptr, nullptr));
   }

@@ -70,6 +70,10 @@ hipError_t sdr_launch_fe_mfma(const FeLaunch& a, hipStream_t st);
 bool sdr_mfma_fragments(const float* h, int T, std::vector<int>* out);
 hipError_t sdr_launch_fe_mono_mfma(const FeLaunch& a, const float* ataps_rev, int TA, int DA, float* audio,
                                    int64_t audio_stride, hipStream_t st);
+// nstreams rows of n complex u8 samples, `stride` complex samples apart, as f32 ((u8 - 128) / 128)
+// rows out_stride complex samples apart
+hipError_t sdr_launch_iq_u8_f32(const void* iq, int64_t n, int64_t stride, int nstreams, float* out, int64_t out_stride,
+                                hipStream_t st);
 hipError_t sdr_launch_iq_zf(const void* iq, int u8, int64_t n, int64_t stride, int nstreams,
                             const double* b_dev, int T, const double* zi_i, const double* zi_q,
                             int64_t zi_stride, double* zf_i, double* zf_q, hipStream_t st);
