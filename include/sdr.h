@@ -811,6 +811,64 @@ int sdr_rds_clock_bits(sdr_rds_clock* clk, uint8_t** dev, int64_t* stride, int32
 int sdr_rds_clock_fetch(sdr_rds_clock* clk, uint8_t* bits, int32_t* counts);
 int sdr_rds_clock_state(sdr_rds_clock* clk, int64_t* state);
 
+/* ---- RDS carrier phase recovery on the device, in front of the symbol clock ---------------
+ * Every stream's rrc_i and rrc_q rows (24 samples a symbol) -> one row per stream, the samples
+ * projected onto the axis the data lie on, left in device memory for sdr_rds_clock_process_dev or
+ * sdr_rds_links_process_dev; n samples in give n samples out.  The clock, the link layer and the
+ * block synchroniser read the in-phase row only: with the 57 kHz carrier's phase off, the symbol
+ * energy is in rrc_q.  The host model rdscarrier.py RdsCarrierPhase is the specification; rows,
+ * state and moments equal it after every call, whatever the split of a stream into calls
+ * (csrc/rds_carrier.hip, four launches per call).  A stream is cut into the clock's segments of
+ * 768 samples on its absolute sample grid; the axis of a segment comes from the complete segments
+ * before it.
+ *   Moments of a complete segment g, the samples widened to f64, a pair with a non-finite value
+ *     counting as (0, 0): Sii, Sqq, Siq from i i, q q, i q -- for each p = 0 .. 23 the sum over
+ *     j = 0 .. 31 ascending of the product at sample 768 g + 24 j + p, then the 24 sums, p ascending.
+ *   Window: for g >= 1, A, B, C = the sums of Sii, Sqq, Siq over the min(window, g) segments before
+ *     g, oldest first; P = A - B, Q = 2 C.
+ *   Direction: khat in 0 .. 31, the sector (11.25 degrees wide, centred on the multiples of 11.25
+ *     degrees) of the doubled angle atan2(Q, P): a = |P|, b = |Q|, swapped if b > a; if not a > 0
+ *     the segment holds kappa and `holds` counts it; m = how many t of tan(pi/32), tan(3 pi/32),
+ *     tan(5 pi/32), tan(7 pi/32) (decimal literals) give b > a t; m = 8 - m if swapped, 16 - m if
+ *     P < 0, (32 - m) mod 32 if Q < 0.
+ *   Tracking: the axis index kappa in 0 .. 63, angle pi kappa / 32.  Segment 0 uses 0, segment 1
+ *     sets kappa = khat, later kappa moves one step (mod 64) towards khat (known mod 32) the
+ *     shorter way when they are 2 or more apart: at most 5.625 degrees per 13.5 ms, 417 degrees/s.
+ *   Output: y[v] = float32(f64(c) f64(i[v]) + f64(s) f64(q[v])) for every sample v of segment g,
+ *     complete or not, (c, s) = entry kappa_g of the axis table, the samples as they are.
+ *   Axis table: 64 float32 pairs (c, s); entries 0 .. 8 are cos and sin of pi kappa / 32 in f64
+ *     rounded to float32, entry 0 (1, 0), entry 8 float32(sqrt(1/2)) twice, the others by symmetry,
+ *     so entry 16 is exactly (0, 1).
+ * sdr_rds_carrier_create: nstreams 1 .. SDR_RDS_CLOCK_MAX_STREAMS, max_n 1 .. SDR_RDS_CLOCK_MAX_N.
+ * sdr_rds_carrier_set_params: window 1 .. SDR_RDS_CARRIER_MAX_WINDOW (default 8), for the calls
+ *   that follow.
+ * sdr_rds_carrier_process_dev: async on the context stream, nothing is read back.  Row s of i and
+ *   of q is the n floats at rrc_i + s * stride and rrc_q + s * stride, each at any 4-byte
+ *   alignment; 0 <= n <= max_n, stride >= n; nothing beyond n is read.
+ * sdr_rds_carrier_rows: the rows the next stage reads: row s is the last call's n floats at
+ *   *dev + s * *stride (16-byte aligned).  Either pointer may be NULL.
+ * sdr_rds_carrier_fetch (synchronises): rows[nstreams][n], the first n <= max_n floats of every row.
+ * sdr_rds_carrier_state (synchronises): state[nstreams][SDR_RDS_CARRIER_NSTATE] = samples taken,
+ *   complete segments, kappa of the last complete segment, steps forward, steps back, holds,
+ *   wraps (steps 63 <-> 0) since reset.
+ * sdr_rds_carrier_moments (synchronises): abc[nstreams][3] = (A, B, C) of the window behind the
+ *   last complete segment's direction (zeros before segment 1);
+ *   sqrt((A - B)^2 + (2 C)^2) / (A + B) is a lock measure.
+ * sdr_rds_carrier_axes: the axis table, out[2 kappa] = c, out[2 kappa + 1] = s. */
+#define SDR_RDS_CARRIER_MAX_WINDOW 16
+#define SDR_RDS_CARRIER_NSTATE 7
+typedef struct sdr_rds_carrier sdr_rds_carrier;
+int sdr_rds_carrier_create(sdr_ctx* ctx, int nstreams, int64_t max_n, sdr_rds_carrier** out);
+void sdr_rds_carrier_destroy(sdr_rds_carrier* car);
+int sdr_rds_carrier_reset(sdr_rds_carrier* car);
+int sdr_rds_carrier_set_params(sdr_rds_carrier* car, int window);
+int sdr_rds_carrier_process_dev(sdr_rds_carrier* car, const float* rrc_i, const float* rrc_q, int64_t n, int64_t stride);
+int sdr_rds_carrier_rows(sdr_rds_carrier* car, float** dev, int64_t* stride);
+int sdr_rds_carrier_fetch(sdr_rds_carrier* car, float* rows, int64_t n);
+int sdr_rds_carrier_state(sdr_rds_carrier* car, int64_t* state);
+int sdr_rds_carrier_moments(sdr_rds_carrier* car, double* abc);
+int sdr_rds_carrier_axes(float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ RX_STAGES = ("fe", "filters_of_demod", "rds_square", "pll", "mix_lpf", "resample
 # device-side RDS link layer (include/sdr.h sdr_rds_links_*)
 SDR_RDS_LINKS_MIN_N, SDR_RDS_LINKS_FAULT, SDR_RDS_LINKS_OVERFLOW = 1536, 1, 2
 SDR_RDS_CLOCK_NSTATE = 10
+SDR_RDS_CARRIER_NSTATE = 7
 PLL_STATS = ("recurrences", "spec_r0", "spec_r1", "spec_r2", "sequential", "long_guessed", "long_chained",
              "long_maxgap", "long_stops", "long_tail", "long_linear")
 
@@ -186,6 +187,16 @@ SIGNATURES = {
     "sdr_rds_clock_bits": (_i32, [_vp, _c.POINTER(_vp), _c.POINTER(_i64), _c.POINTER(_vp), _c.POINTER(_i64)]),
     "sdr_rds_clock_fetch": (_i32, [_vp, _vp, _vp]),
     "sdr_rds_clock_state": (_i32, [_vp, _vp]),
+    "sdr_rds_carrier_create": (_i32, [_vp, _i32, _i64, _c.POINTER(_vp)]),
+    "sdr_rds_carrier_destroy": (None, [_vp]),
+    "sdr_rds_carrier_reset": (_i32, [_vp]),
+    "sdr_rds_carrier_set_params": (_i32, [_vp, _i32]),
+    "sdr_rds_carrier_process_dev": (_i32, [_vp, _vp, _vp, _i64, _i64]),
+    "sdr_rds_carrier_rows": (_i32, [_vp, _c.POINTER(_vp), _c.POINTER(_i64)]),
+    "sdr_rds_carrier_fetch": (_i32, [_vp, _vp, _i64]),
+    "sdr_rds_carrier_state": (_i32, [_vp, _vp]),
+    "sdr_rds_carrier_moments": (_i32, [_vp, _vp]),
+    "sdr_rds_carrier_axes": (_i32, [_vp]),
 }
 
 _lib = None

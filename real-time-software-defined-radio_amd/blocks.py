@@ -396,6 +396,15 @@ class Receiver(_Handle):
         kw.setdefault("ctx", self.ctx)
         return RdsClockBank(self.S, self._length("rrc_i"), **kw)
 
+    def rds_carrier(self, **kw) -> "RdsCarrierBank":
+        """A device-side RDS carrier phase stage sized to this receiver (RdsCarrierBank: one stream
+        per receiver stream, rows of the "rrc_i" length); per block carrier.process_rx(receiver),
+        then carrier.feed(clock) with clock = carrier.clock().  Needs rds=True."""
+        if not self.flags & SDR_RX_RDS:
+            raise ValueError("rds_carrier needs a receiver with rds=True")
+        kw.setdefault("ctx", self.ctx)
+        return RdsCarrierBank(self.S, self._length("rrc_i"), **kw)
+
     def mpx_spectrum(self, nfft: int = 1024, hop=None, navg: int = 0, **kw) -> "RowSpectrum":
         """A RowSpectrum sized to this receiver's "demod" rows (one row per stream, the multiplex at
         design.AUDIO_FS; hop defaults to nfft / 2); feed it with spectrum.process_rx(receiver,
@@ -764,6 +773,98 @@ class RdsClockBank(_Handle):
         if sync.S != self.S:
             raise ValueError(f"the sync has {sync.S} streams, the bank {self.S}")
         sync.process_dev(self.bits_ptr, self.max_bits, self.bits_stride, self.counts_ptr)
+
+
+class RdsCarrierBank(_Handle):
+    """RDS carrier phase recovery for `nstreams` streams at once, on the GPU (sdr_rds_carrier,
+    csrc/rds_carrier.hip): the "rrc_i" and "rrc_q" rows are read where the receiver left them, and
+    one row per stream -- the samples projected onto the axis the data lie on -- stays in device
+    memory for RdsClockBank.process_dev or RdsLinkBank.process_dev: feed(bank).  n samples in give
+    n samples out.  rdscarrier.RdsCarrierPhase is the specification: rows, state and moments equal
+    it after every call, whatever the split.
+
+    max_n: the longest row a call may bring (0 <= n <= max_n).  window: as RdsCarrierPhase's.
+    rows_ptr, rows_stride: the device rows, rows_stride floats apart."""
+
+    _prefix = "sdr_rds_carrier"
+
+    def __init__(self, nstreams: int, max_n: int, window: int = 8, ctx=None):
+        self.S, self.max_n = int(nstreams), int(max_n)
+        self.ctx = ctx if ctx is not None else _lib.get_context()
+        self.lib = self.ctx.lib
+        self.n = 0                                                # the last call's
+        h = ctypes.c_void_p()
+        check(self.lib.sdr_rds_carrier_create(self.ctx.handle, self.S, self.max_n, ctypes.byref(h)), "sdr_rds_carrier_create")
+        self.handle = h
+        try:
+            self.set_params(window)
+            dev, stride = ctypes.c_void_p(), ctypes.c_int64()
+            self._do("rows", ctypes.byref(dev), ctypes.byref(stride))
+        except Exception:
+            self.close()
+            raise
+        self.rows_ptr, self.rows_stride = dev.value, stride.value
+
+    def set_params(self, window: int):
+        """For the calls that follow (the model takes it at construction: set it before the first
+        call to equal it)."""
+        self._do("set_params", int(window))
+        self.window = int(window)
+
+    def process_dev(self, i_ptr: int, q_ptr: int, n: int, stride: int):
+        """One call for every stream: row s of i and of q is the n floats at device pointer
+        i_ptr + 4 s stride and q_ptr + 4 s stride, 0 <= n <= max_n.  Async on the context stream."""
+        self._do("process_dev", i_ptr, q_ptr, int(n), int(stride))
+        self.n = int(n)
+
+    def process_rx(self, receiver: "Receiver"):
+        """The receiver's latest "rrc_i" and "rrc_q" rows (looked up at every call: a pipelined
+        receiver alternates its row sets)."""
+        if receiver.S != self.S:
+            raise ValueError(f"the receiver has {receiver.S} streams, the bank {self.S}")
+        pi, stride, n = receiver.output_ptr("rrc_i")
+        pq, stride_q, n_q = receiver.output_ptr("rrc_q")
+        if (stride_q, n_q) != (stride, n):
+            raise ValueError("the receiver's rrc_i and rrc_q rows differ in shape")
+        self.process_dev(pi, pq, n, stride)
+
+    def rows(self) -> np.ndarray:
+        """The last call's rows, after waiting for it: (nstreams, n) float32."""
+        out = np.empty((self.S, self.n), dtype=np.float32)
+        self._do("fetch", out.ctypes.data, self.n)
+        return out
+
+    def state(self):
+        """Per stream (consumed samples, complete segments, kappa, steps forward, steps back, holds,
+        wraps) -- RdsCarrierPhase.state() -- after waiting for the last call."""
+        st = np.zeros((self.S, _lib.SDR_RDS_CARRIER_NSTATE), dtype=np.int64)
+        self._do("state", st.ctypes.data)
+        return [tuple(int(v) for v in row) for row in st]
+
+    def moments(self):
+        """Per stream (A, B, C) of the window behind the last complete segment's direction --
+        RdsCarrierPhase.moments() -- after waiting for the last call."""
+        m = np.zeros((self.S, 3), dtype=np.float64)
+        self._do("moments", m.ctypes.data)
+        return [tuple(float(v) for v in row) for row in m]
+
+    def reset(self):
+        """Every stream back to sample 0; the counters to 0."""
+        self._do("reset")
+        self.n = 0
+
+    def feed(self, bank):
+        """The last call's rows into an RdsClockBank or an RdsLinkBank, device to device.  Async on
+        the context stream; call it once after each call."""
+        if bank.S != self.S:
+            raise ValueError(f"the bank has {bank.S} streams, the carrier stage {self.S}")
+        bank.process_dev(self.rows_ptr, self.n, self.rows_stride)
+
+    def clock(self, **kw) -> "RdsClockBank":
+        """A device-side symbol clock sized to this bank; feed it with bank.feed(clock) after each
+        call."""
+        kw.setdefault("ctx", self.ctx)
+        return RdsClockBank(self.S, self.max_n, **kw)
 
 
 def rds_groups(events):
