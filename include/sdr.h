@@ -443,6 +443,64 @@ int sdr_rx_state(sdr_rx* rx, double* phase, double* pll_stereo, double* pll_rds)
 /* sdr_pll_stats of the receiver's context, after waiting for every block in flight */
 int sdr_rx_pll_stats(sdr_rx* rx, int64_t* out, int reset);
 
+/* ---- IQ imbalance and DC offset correction of the capture -----------------------------------
+ * The stage in front of sdr_spec / sdr_ddc / sdr_pfb: one block of a capture in device memory
+ * (interleaved f32, or u8 as (x - 128) / 128) in, the same block as interleaved f32 out, with the
+ * front end's DC offset removed and the Q branch's gain and phase error undone -- what keeps a
+ * station at +f from leaving an image at -f in another channel of the bank, and the ADC's zero
+ * out of the centre bin.  The estimate is blind: a sum of stations away from 0 Hz is a proper
+ * complex signal (E[z^2] = 0), so whatever its second moments show beyond equal, uncorrelated I
+ * and Q is the front end's, and one 2 x 2 real matrix undoes it.  The model is frequency-
+ * independent: one matrix for the whole band.  The reference has no such stage; the definition
+ * is rtsdr.IqBalance (iqbalance.py), in f64:
+ *   state: smoothed raw moments m = (mI, mQ, pII, pQQ, pIQ); coefficients (dI, dQ, c1, c2),
+ *   initially (0, 0, 0, 1); counters updates, skipped, holds.  A call of n samples, estimate != 0:
+ *   1. r = (sum I, sum Q, sum I^2, sum Q^2, sum I Q) / n over the block.
+ *   2. any of the five not finite: skipped += 1 and nothing else changes.  Else m = r on the
+ *      first update, m = m + rate (r - m) later; updates += 1.
+ *   3. A = pII - mI mI, B = pQQ - mQ mQ, C = pIQ - mI mQ, t = B - (C / A) C.  If A > 0, t > 0 and
+ *      both are finite: c2 = sqrt(A / t), c1 = -(C / A) c2, dI = mI, dQ = mQ (dc == 0: dI = dQ = 0
+ *      are installed; balance == 0: c1 = 0, c2 = 1).  Else the coefficients stay, holds += 1 (an
+ *      all-zero block, a constant block, Q = I).
+ *   4. the same block, with the coefficients just computed:
+ *      I' = f32(I - dI), Q' = f32(c1 (I - dI) + c2 (Q - dQ)), evaluated in f64 as written and
+ *      rounded once.  A NaN sample stays a NaN at that sample only.
+ *   estimate == 0: step 4 only.  sdr_iqc_set installs coefficients (a front end calibrated once),
+ *   sdr_iqc_reset returns to the initial state.
+ * Three launches per call (csrc/iqc.hip: moments, update, apply), no host synchronisation, no
+ * atomics: the same call gives the same bits.  The u8 moments are integer sums, so they equal
+ * the definition's exactly; the f32 sums are f64 sums in the kernel's fixed order.  The block is
+ * cut into at most 2 048 chunks, none but the last shorter than SDR_IQC_CHUNK samples, one
+ * workgroup each.  sdr_iqc_process_dev: async; iq aligned to one complex sample (8 B f32, 2 B
+ * u8), out to 8 B; out is the buffer sdr_spec / sdr_ddc / sdr_pfb_process_dev read.  For f32,
+ * out == iq (in place) is allowed; any other overlap is refused.  n <= 2^31 - 1; all sample
+ * offsets are 64-bit.  sdr_iqc_state (host [SDR_IQC_NSTATE]: mI mQ pII pQQ pIQ dI dQ c1 c2 updates
+ * skipped holds) synchronises; sdr_iqc_coeffs_dev: the device array dI dQ c1 c2.
+ * SDR_EINVAL (before any device work): NULL pointers, bad dtype, rate outside (0, 1] or not
+ * finite, a non-finite coefficient, n < 1, a misaligned pointer, partial overlap.  No host
+ * fallback. */
+#define SDR_IQC_NSTATE 12
+#define SDR_IQC_CHUNK 4096
+typedef struct sdr_iqc_params {
+  double rate;   /* the share of the way to the block's moments the smoothed ones move, in (0, 1] */
+  int dc;        /* remove the DC offset */
+  int balance;   /* undo the gain and phase error */
+} sdr_iqc_params;  /* NULL: 0.125, 1, 1 */
+typedef struct sdr_iqc sdr_iqc;
+int  sdr_iqc_create(sdr_ctx* ctx, int iq_dtype /* SDR_IQ_F32 | SDR_IQ_U8 */, const sdr_iqc_params* params, sdr_iqc** out);
+void sdr_iqc_destroy(sdr_iqc* iqc);
+int  sdr_iqc_reset(sdr_iqc* iqc);                                            /* async */
+int  sdr_iqc_set(sdr_iqc* iqc, const double coeff[4] /* dI dQ c1 c2, finite */); /* async */
+int  sdr_iqc_process_dev(sdr_iqc* iqc, const void* iq, int64_t n, float* out, int estimate);   /* async */
+int  sdr_iqc_run(sdr_iqc* iqc, const void* iq_host, int64_t n, float* out_host, int estimate); /* sync */
+int  sdr_iqc_state(sdr_iqc* iqc, double* host /* [SDR_IQC_NSTATE] */);       /* synchronises */
+int  sdr_iqc_coeffs_dev(sdr_iqc* iqc, const double** dev /* dI dQ c1 c2 */);
+/* per-launch timing of the last call made with an estimate (HIP events between the three launches,
+ * on the context stream): moments, update, apply; ms: 3 floats.  Timing adds event records between
+ * launches; keep it off in measured loops. */
+int  sdr_iqc_set_timing(sdr_iqc* iqc, int on);
+int  sdr_iqc_stage_ms(sdr_iqc* iqc, float* ms);
+
 /* ---- wideband channelizer (multi-channel digital down-converter) ---------------------
  * One interleaved-IQ capture (f32, or u8 as (x-128)/128) in, nch rows of interleaved complex
  * f32 at Fs/decim out, row c centred on freq[c]: per channel "mix down, lfilter(b, 1, .),

@@ -34,6 +34,7 @@ RX_STAGES = ("fe", "filters_of_demod", "rds_square", "pll", "mix_lpf", "resample
 SDR_RDS_LINKS_MIN_N, SDR_RDS_LINKS_FAULT, SDR_RDS_LINKS_OVERFLOW = 1536, 1, 2
 SDR_RDS_CLOCK_NSTATE = 10
 SDR_RDS_CARRIER_NSTATE = 7
+SDR_IQC_NSTATE, SDR_IQC_CHUNK = 12, 4096   # the corrector of the capture (include/sdr.h sdr_iqc_*)
 PLL_STATS = ("recurrences", "spec_r0", "spec_r1", "spec_r2", "sequential", "long_guessed", "long_chained",
              "long_maxgap", "long_stops", "long_tail", "long_linear")
 
@@ -130,6 +131,16 @@ SIGNATURES = {
     "sdr_rx_pll_stats": (_i32, [_vp, _vp, _i32]),
     "sdr_rx_set_timing": (_i32, [_vp, _i32]),
     "sdr_rx_stage_ms": (_i32, [_vp, _fp]),
+    "sdr_iqc_create": (_i32, [_vp, _i32, _vp, _c.POINTER(_vp)]),
+    "sdr_iqc_destroy": (None, [_vp]),
+    "sdr_iqc_reset": (_i32, [_vp]),
+    "sdr_iqc_set": (_i32, [_vp, _dp]),
+    "sdr_iqc_process_dev": (_i32, [_vp, _vp, _i64, _vp, _i32]),
+    "sdr_iqc_run": (_i32, [_vp, _vp, _i64, _vp, _i32]),
+    "sdr_iqc_state": (_i32, [_vp, _dp]),
+    "sdr_iqc_coeffs_dev": (_i32, [_vp, _c.POINTER(_vp)]),
+    "sdr_iqc_set_timing": (_i32, [_vp, _i32]),
+    "sdr_iqc_stage_ms": (_i32, [_vp, _fp]),
     "sdr_ddc_create": (_i32, [_vp, _i32, _dp, _dp, _i32, _i32, _i32, _c.POINTER(_vp)]),
     "sdr_ddc_destroy": (None, [_vp]),
     "sdr_ddc_freq": (_i32, [_vp, _dp]),

@@ -23,6 +23,7 @@ import numpy as np
 
 from . import _lib
 from . import design
+from . import iqbalance
 from ._lib import RX_FILTERS, RX_OUTPUTS, SDR_IQ_F32, SDR_IQ_U8, SDR_RX_AUDIO, SDR_RX_RDS, SDR_RX_STEREO, check, f64p
 from .dsp import _taps
 
@@ -877,6 +878,121 @@ def rds_groups(events):
         if t == 0 and all((p + 26 * k, k) in ok for k in (1, 2, 3)):
             groups.append(tuple(ok[(p + 26 * k, k)] for k in range(4)))
     return groups
+
+
+class _IqcParamsC(ctypes.Structure):                             # include/sdr.h sdr_iqc_params
+    _fields_ = [("rate", ctypes.c_double), ("dc", ctypes.c_int), ("balance", ctypes.c_int)]
+
+
+class IqCorrector(_Handle):
+    """IQ imbalance and DC offset correction of a capture block on the GPU (sdr_iqc, csrc/iqc.hip):
+    the stage in front of Spectrum, Channelizer and FilterBank.  A direct-conversion front end's Q
+    branch has a slightly different gain and is not quite 90 degrees from I, so every station at +f
+    leaves an image at -f, in another channel of the bank; and the ADC's zero is not zero, a carrier
+    in the centre bin.  process_dev reads a block in device memory (interleaved float32, or uint8
+    as (x - 128) / 128), estimates both from the block's five second moments, smooths the estimate
+    over calls by `rate`, and writes the corrected block as interleaved float32 -- the buffer the
+    stages behind it read.  Three launches, nothing returns to the host unless state() is asked.
+
+    The rule is rtsdr.IqBalance's (iqbalance.py), step for step; it is blind (no pilot, no
+    calibration tone) and frequency-independent: one 2 x 2 matrix for the whole band.  dc=False /
+    balance=False leave that half of the correction out.  estimate=False applies the coefficients
+    in force without looking at the block; set() installs coefficients of a front end calibrated
+    once.  For float32, out_ptr == iq_ptr (in place) is allowed.  The arguments are checked before
+    a context exists; the device object is made at the first call that needs it."""
+
+    NSTATE = _lib.SDR_IQC_NSTATE
+    CHUNK = _lib.SDR_IQC_CHUNK                                   # samples of a workgroup's chunk (at least)
+    MAX_N = 2 ** 31 - 1
+    _prefix = "sdr_iqc"
+
+    def __init__(self, iq_dtype=np.float32, rate: float = iqbalance.DEFAULT_RATE, dc: bool = True, balance: bool = True, ctx=None):
+        self.u8 = _is_u8(iq_dtype)
+        self.rate, self.dc, self.balance = iqbalance.check_rate(rate), bool(dc), bool(balance)
+        self._ctx = ctx
+
+    def _open(self):
+        if self.handle is None:
+            self.ctx = self._ctx if self._ctx is not None else _lib.get_context()
+            self.lib = self.ctx.lib
+            h = ctypes.c_void_p()
+            prm = _IqcParamsC(self.rate, int(self.dc), int(self.balance))
+            check(self.lib.sdr_iqc_create(self.ctx.handle, SDR_IQ_U8 if self.u8 else SDR_IQ_F32, ctypes.byref(prm), ctypes.byref(h)),
+                  "sdr_iqc_create")
+            self.handle = h
+        return self.handle
+
+    def process_dev(self, iq_ptr: int, n: int, out_ptr: int, estimate: bool = True):
+        """n complex samples at device pointer iq_ptr -> n corrected complex float32 at out_ptr;
+        async on the context stream."""
+        n, iq_ptr, out_ptr = int(n), int(iq_ptr or 0), int(out_ptr or 0)
+        es = 2 if self.u8 else 8
+        if not iq_ptr or not out_ptr:
+            raise ValueError("iq_ptr or out_ptr is NULL")
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError(f"n={n} outside [1, 2^31 - 1]")
+        if iq_ptr % es or out_ptr % 8:
+            raise ValueError(f"iq_ptr must be aligned to one complex sample ({es} B) and out_ptr to 8 B")
+        if iq_ptr < out_ptr + 8 * n and out_ptr < iq_ptr + es * n and not (not self.u8 and iq_ptr == out_ptr):
+            raise ValueError("iq and out overlap (only out_ptr == iq_ptr of a float32 corrector may)")
+        h = self._open()
+        check(self.lib.sdr_iqc_process_dev(h, iq_ptr, n, out_ptr, int(bool(estimate))), "sdr_iqc_process_dev")
+
+    def run(self, iq, estimate: bool = True) -> np.ndarray:
+        """n complex samples from the host (interleaved f32 / u8, or complex for a float32 object)
+        -> the corrected block, interleaved float32 (2 n values); synchronous (sdr_iqc_run)."""
+        iq = _interleaved_iq(iq, self.u8, "corrector")
+        n = iq.size // 2
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError(f"n={n} outside [1, 2^31 - 1]")
+        out = np.empty(2 * n, dtype=np.float32)
+        h = self._open()
+        check(self.lib.sdr_iqc_run(h, iq.ctypes.data, n, out.ctypes.data, int(bool(estimate))), "sdr_iqc_run")
+        return out
+
+    def raw_state(self) -> np.ndarray:
+        """The 12 float64 values mI mQ pII pQQ pIQ dI dQ c1 c2 updates skipped holds (sdr_iqc_state;
+        synchronises)."""
+        out = np.empty(self.NSTATE)
+        h = self._open()
+        check(self.lib.sdr_iqc_state(h, f64p(out)), "sdr_iqc_state")
+        return out
+
+    def state(self) -> "iqbalance.IqState":
+        """The state as IqBalance.state() gives it: the 12 values, and impropriety / image_db of the
+        smoothed moments computed on the host."""
+        return iqbalance.make_state(self.raw_state())
+
+    def set(self, dI: float, dQ: float, c1: float, c2: float):
+        """Install coefficients (async); the next estimate replaces them."""
+        c = np.array(iqbalance.check_coeffs((dI, dQ, c1, c2)))
+        h = self._open()
+        check(self.lib.sdr_iqc_set(h, f64p(c)), "sdr_iqc_set")
+
+    def reset(self):
+        """Back to the state after creation (async)."""
+        h = self._open()
+        check(self.lib.sdr_iqc_reset(h), "sdr_iqc_reset")
+
+    def set_timing(self, on: bool = True):
+        """HIP events between the launches of each call (sdr_iqc_set_timing); off in measured loops."""
+        h = self._open()
+        check(self.lib.sdr_iqc_set_timing(h, int(bool(on))), "sdr_iqc_set_timing")
+
+    def stage_ms(self) -> dict:
+        """{moments, update, apply}: milliseconds of the last call made with an estimate (sdr_iqc_stage_ms)."""
+        ms = (ctypes.c_float * 3)()
+        h = self._open()
+        check(self.lib.sdr_iqc_stage_ms(h, ms), "sdr_iqc_stage_ms")
+        return dict(zip(("moments", "update", "apply"), (float(v) for v in ms)))
+
+    @property
+    def coeffs_ptr(self) -> int:
+        """The device array of four float64 dI dQ c1 c2 (sdr_iqc_coeffs_dev)."""
+        p = ctypes.c_void_p()
+        h = self._open()
+        check(self.lib.sdr_iqc_coeffs_dev(h, ctypes.byref(p)), "sdr_iqc_coeffs_dev")
+        return p.value
 
 
 class Channelizer(_DecimBlock):
