@@ -17,6 +17,7 @@ reference loops:
 from __future__ import annotations
 
 import collections
+import contextlib
 import ctypes
 
 import numpy as np
@@ -546,7 +547,52 @@ class RdsLinkLayer(_Handle):
                     diff=diff[:nd.value].copy())
 
 
-class RdsLinkBank(_Handle):
+class _RdsBank(_Handle):
+    """An RDS stage for `S` streams at once on the GPU, every stream's state in device memory: the
+    context, the create with the set-up that follows it, the stream-count rule, the receiver's
+    rows and the int64 state matrix."""
+
+    @contextlib.contextmanager
+    def _create(self, nstreams, ctx, *args):
+        """<prefix>_create(context, S, *args, &handle) on `ctx` (None: the default context); a
+        failure of the set-up in the `with` body closes the object again."""
+        self.S = int(nstreams)
+        self.ctx = ctx if ctx is not None else _lib.get_context()
+        self.lib = self.ctx.lib
+        h = ctypes.c_void_p()
+        name = f"{self._prefix}_create"
+        check(getattr(self.lib, name)(self.ctx.handle, self.S, *args, ctypes.byref(h)), name)
+        self.handle = h
+        try:
+            yield
+        except Exception:
+            self.close()
+            raise
+
+    def _check_streams(self, other, noun, me="bank"):
+        if other.S != self.S:
+            raise ValueError(f"the {noun} has {other.S} streams, the {me} {self.S}")
+
+    def _receiver_rows(self, receiver, *names):
+        """(pointer per name, n, stride) of the receiver's latest rows of those names."""
+        self._check_streams(receiver, "receiver")
+        rows = [receiver.output_ptr(name) for name in names]
+        if any(r[1:] != rows[0][1:] for r in rows):
+            raise ValueError(f"the receiver's {' and '.join(names)} rows differ in shape")
+        return (*(r[0] for r in rows), rows[0][2], rows[0][1])
+
+    def _state_rows(self, ncols):
+        st = np.zeros((self.S, ncols), dtype=np.int64)
+        self._do("state", st.ctypes.data)
+        return [tuple(int(v) for v in row) for row in st]
+
+    def reset(self):
+        """Every stream back to its start (block 0, SEARCH at position 0, sample 0); the counters
+        to 0."""
+        self._do("reset")
+
+
+class RdsLinkBank(_RdsBank):
     """RdsLinkLayer for `nstreams` streams at once, on the GPU (sdr_rds_links, csrc/rds.hip): the
     in-phase RRC rows are read where the receiver left them, every stream's link state stays in
     device memory, and what comes back is the events -- per stream a list of
@@ -567,34 +613,26 @@ class RdsLinkBank(_Handle):
     _prefix = "sdr_rds_links"
 
     def __init__(self, nstreams: int, max_n: int, *, max_events=None, resync_after: int = 0, ctx=None):
-        self.S, self.max_n = int(nstreams), int(max_n)
+        self.max_n = int(max_n)
         # a call scans at most (max_n / 24) / 2 + 2 windows, and a window gives at most two events
         self.max_events = int(max_events) if max_events is not None else min(2 * (self.max_n // 48 + 4), 4096)
-        self.ctx = ctx if ctx is not None else _lib.get_context()
-        self.lib = self.ctx.lib
-        h = ctypes.c_void_p()
-        check(self.lib.sdr_rds_links_create(self.ctx.handle, self.S, self.max_n, self.max_events, ctypes.byref(h)),
-              "sdr_rds_links_create")
-        self.handle = h
-        self.counts = np.zeros(self.S, dtype=np.int64)
-        if resync_after:
-            self.set_resync(resync_after)
+        with self._create(nstreams, ctx, self.max_n, self.max_events):
+            self.counts = np.zeros(self.S, dtype=np.int64)
+            if resync_after:
+                self.set_resync(resync_after)
 
     def set_resync(self, after_bad_syncs: int):
-        check(self.lib.sdr_rds_links_set_resync(self.handle, int(after_bad_syncs)), "sdr_rds_links_set_resync")
+        self._do("set_resync", int(after_bad_syncs))
 
     def process_dev(self, ptr: int, n: int, stride: int):
         """One call for every stream: row s is the n floats at device pointer ptr + 4 s stride.
         Async on the context stream."""
-        check(self.lib.sdr_rds_links_process_dev(self.handle, ptr, int(n), int(stride)), "sdr_rds_links_process_dev")
+        self._do("process_dev", ptr, int(n), int(stride))
 
     def process_rx(self, receiver: "Receiver"):
         """The receiver's latest "rrc_i" rows (looked up at every call: a pipelined receiver
         alternates its row sets)."""
-        if receiver.S != self.S:
-            raise ValueError(f"the receiver has {receiver.S} streams, the bank {self.S}")
-        ptr, stride, n = receiver.output_ptr("rrc_i")
-        self.process_dev(ptr, n, stride)
+        self.process_dev(*self._receiver_rows(receiver, "rrc_i"))
 
     def events(self):
         """(events, status) of the last call, after waiting for it: events[s] the stream's list of
@@ -603,8 +641,7 @@ class RdsLinkBank(_Handle):
         ev = np.zeros((self.S, self.max_events, 4), dtype=np.int64)
         ne = np.zeros(self.S, dtype=np.int64)
         status = np.zeros(self.S, dtype=np.int32)
-        check(self.lib.sdr_rds_links_events(self.handle, ev.ctypes.data, ne.ctypes.data, status.ctypes.data),
-              "sdr_rds_links_events")
+        self._do("events", ev.ctypes.data, ne.ctypes.data, status.ctypes.data)
         self.counts = ne
         return [[tuple(e) for e in ev[s, :min(int(ne[s]), self.max_events)].tolist()] for s in range(self.S)], status
 
@@ -614,13 +651,8 @@ class RdsLinkBank(_Handle):
         nb_max = self.max_n // 48 + 2
         bits, diff = np.empty(nb_max, dtype=np.uint8), np.empty(nb_max + 32, dtype=np.uint8)
         nb, nd = ctypes.c_int64(), ctypes.c_int64()
-        check(self.lib.sdr_rds_links_bits(self.handle, int(stream), bits.ctypes.data, len(bits), ctypes.byref(nb),
-                                          diff.ctypes.data, len(diff), ctypes.byref(nd)), "sdr_rds_links_bits")
+        self._do("bits", int(stream), bits.ctypes.data, len(bits), ctypes.byref(nb), diff.ctypes.data, len(diff), ctypes.byref(nd))
         return bits[:nb.value].copy(), diff[:nd.value].copy()
-
-    def reset(self):
-        """Every stream back to block 0."""
-        check(self.lib.sdr_rds_links_reset(self.handle), "sdr_rds_links_reset")
 
     def block_sync(self, **kw) -> "RdsSyncBank":
         """A device-side block synchroniser sized to this bank (RdsSyncBank: one stream per link
@@ -630,7 +662,7 @@ class RdsLinkBank(_Handle):
         return RdsSyncBank(self.S, -(-self.max_n // 24) // 2, **kw)
 
 
-class RdsSyncBank(_Handle):
+class RdsSyncBank(_RdsBank):
     """RDS block synchronisation for `nstreams` streams at once, on the GPU (sdr_rds_sync,
     csrc/rds_sync.hip): acquisition, flywheel, burst correction and offset C' over every stream's
     differential bits, all state in device memory.  rdssync.RdsBlockSync is the specification:
@@ -644,18 +676,10 @@ class RdsSyncBank(_Handle):
     _prefix = "sdr_rds_sync"
 
     def __init__(self, nstreams: int, max_bits: int, max_burst: int = 2, lose_after: int = 12, ctx=None):
-        self.S, self.max_bits = int(nstreams), int(max_bits)
+        self.max_bits = int(max_bits)
         self.max_records = self.max_bits // 26 + 3
-        self.ctx = ctx if ctx is not None else _lib.get_context()
-        self.lib = self.ctx.lib
-        h = ctypes.c_void_p()
-        check(self.lib.sdr_rds_sync_create(self.ctx.handle, self.S, self.max_bits, ctypes.byref(h)), "sdr_rds_sync_create")
-        self.handle = h
-        try:
+        with self._create(nstreams, ctx, self.max_bits):
             self.set_params(max_burst, lose_after)
-        except Exception:
-            self.close()
-            raise
 
     def set_params(self, max_burst: int, lose_after: int):
         self._do("set_params", int(max_burst), int(lose_after))
@@ -688,12 +712,8 @@ class RdsSyncBank(_Handle):
         self._do("state", synced.ctypes.data, pos.ctypes.data, cnt.ctypes.data)
         return [(int(synced[s]), int(pos[s]), *(int(v) for v in cnt[s])) for s in range(self.S)]
 
-    def reset(self):
-        """Every stream back to SEARCH at position 0; the counters to 0."""
-        self._do("reset")
 
-
-class RdsClockBank(_Handle):
+class RdsClockBank(_RdsBank):
     """RDS symbol clock recovery for `nstreams` streams at once, on the GPU (sdr_rds_clock,
     csrc/rds_clock.hip): the in-phase RRC rows are read where the receiver left them, and every
     stream's differential bits (byte per bit) and an int32 count per stream stay in device memory
@@ -708,20 +728,12 @@ class RdsClockBank(_Handle):
     _prefix = "sdr_rds_clock"
 
     def __init__(self, nstreams: int, max_n: int, window: int = 4, hysteresis: int = 8, ctx=None):
-        self.S, self.max_n = int(nstreams), int(max_n)
-        self.ctx = ctx if ctx is not None else _lib.get_context()
-        self.lib = self.ctx.lib
-        h = ctypes.c_void_p()
-        check(self.lib.sdr_rds_clock_create(self.ctx.handle, self.S, self.max_n, ctypes.byref(h)), "sdr_rds_clock_create")
-        self.handle = h
-        try:
+        self.max_n = int(max_n)
+        with self._create(nstreams, ctx, self.max_n):
             self.set_params(window, hysteresis)
             dev, cnt = ctypes.c_void_p(), ctypes.c_void_p()
             stride, mb = ctypes.c_int64(), ctypes.c_int64()
             self._do("bits", ctypes.byref(dev), ctypes.byref(stride), ctypes.byref(cnt), ctypes.byref(mb))
-        except Exception:
-            self.close()
-            raise
         self.bits_ptr, self.bits_stride, self.counts_ptr, self.max_bits = dev.value, stride.value, cnt.value, mb.value
 
     def set_params(self, window: int, hysteresis: int):
@@ -738,10 +750,7 @@ class RdsClockBank(_Handle):
     def process_rx(self, receiver: "Receiver"):
         """The receiver's latest "rrc_i" rows (looked up at every call: a pipelined receiver
         alternates its row sets)."""
-        if receiver.S != self.S:
-            raise ValueError(f"the receiver has {receiver.S} streams, the bank {self.S}")
-        ptr, stride, n = receiver.output_ptr("rrc_i")
-        self.process_dev(ptr, n, stride)
+        self.process_dev(*self._receiver_rows(receiver, "rrc_i"))
 
     def bits(self):
         """The last call's differential bits, after waiting for it: per stream a uint8 array."""
@@ -753,13 +762,7 @@ class RdsClockBank(_Handle):
     def state(self):
         """Per stream (consumed samples, segments, phi, pi, symbols, bits, steps forward, steps
         back, wraps, pairing changes) -- RdsSymbolClock.state() -- after waiting for the last call."""
-        st = np.zeros((self.S, _lib.SDR_RDS_CLOCK_NSTATE), dtype=np.int64)
-        self._do("state", st.ctypes.data)
-        return [tuple(int(v) for v in row) for row in st]
-
-    def reset(self):
-        """Every stream back to sample 0; the counters to 0."""
-        self._do("reset")
+        return self._state_rows(_lib.SDR_RDS_CLOCK_NSTATE)
 
     def block_sync(self, **kw) -> "RdsSyncBank":
         """A device-side block synchroniser sized to this bank (RdsSyncBank: one stream per clock
@@ -771,12 +774,11 @@ class RdsClockBank(_Handle):
     def feed(self, sync: "RdsSyncBank"):
         """The last call's bits into the block synchroniser, device to device: every stream takes
         its own count.  Async on the context stream; call it once after each call."""
-        if sync.S != self.S:
-            raise ValueError(f"the sync has {sync.S} streams, the bank {self.S}")
+        self._check_streams(sync, "sync")
         sync.process_dev(self.bits_ptr, self.max_bits, self.bits_stride, self.counts_ptr)
 
 
-class RdsCarrierBank(_Handle):
+class RdsCarrierBank(_RdsBank):
     """RDS carrier phase recovery for `nstreams` streams at once, on the GPU (sdr_rds_carrier,
     csrc/rds_carrier.hip): the "rrc_i" and "rrc_q" rows are read where the receiver left them, and
     one row per stream -- the samples projected onto the axis the data lie on -- stays in device
@@ -790,20 +792,12 @@ class RdsCarrierBank(_Handle):
     _prefix = "sdr_rds_carrier"
 
     def __init__(self, nstreams: int, max_n: int, window: int = 8, ctx=None):
-        self.S, self.max_n = int(nstreams), int(max_n)
-        self.ctx = ctx if ctx is not None else _lib.get_context()
-        self.lib = self.ctx.lib
+        self.max_n = int(max_n)
         self.n = 0                                                # the last call's
-        h = ctypes.c_void_p()
-        check(self.lib.sdr_rds_carrier_create(self.ctx.handle, self.S, self.max_n, ctypes.byref(h)), "sdr_rds_carrier_create")
-        self.handle = h
-        try:
+        with self._create(nstreams, ctx, self.max_n):
             self.set_params(window)
             dev, stride = ctypes.c_void_p(), ctypes.c_int64()
             self._do("rows", ctypes.byref(dev), ctypes.byref(stride))
-        except Exception:
-            self.close()
-            raise
         self.rows_ptr, self.rows_stride = dev.value, stride.value
 
     def set_params(self, window: int):
@@ -821,13 +815,7 @@ class RdsCarrierBank(_Handle):
     def process_rx(self, receiver: "Receiver"):
         """The receiver's latest "rrc_i" and "rrc_q" rows (looked up at every call: a pipelined
         receiver alternates its row sets)."""
-        if receiver.S != self.S:
-            raise ValueError(f"the receiver has {receiver.S} streams, the bank {self.S}")
-        pi, stride, n = receiver.output_ptr("rrc_i")
-        pq, stride_q, n_q = receiver.output_ptr("rrc_q")
-        if (stride_q, n_q) != (stride, n):
-            raise ValueError("the receiver's rrc_i and rrc_q rows differ in shape")
-        self.process_dev(pi, pq, n, stride)
+        self.process_dev(*self._receiver_rows(receiver, "rrc_i", "rrc_q"))
 
     def rows(self) -> np.ndarray:
         """The last call's rows, after waiting for it: (nstreams, n) float32."""
@@ -838,9 +826,7 @@ class RdsCarrierBank(_Handle):
     def state(self):
         """Per stream (consumed samples, complete segments, kappa, steps forward, steps back, holds,
         wraps) -- RdsCarrierPhase.state() -- after waiting for the last call."""
-        st = np.zeros((self.S, _lib.SDR_RDS_CARRIER_NSTATE), dtype=np.int64)
-        self._do("state", st.ctypes.data)
-        return [tuple(int(v) for v in row) for row in st]
+        return self._state_rows(_lib.SDR_RDS_CARRIER_NSTATE)
 
     def moments(self):
         """Per stream (A, B, C) of the window behind the last complete segment's direction --
@@ -851,14 +837,13 @@ class RdsCarrierBank(_Handle):
 
     def reset(self):
         """Every stream back to sample 0; the counters to 0."""
-        self._do("reset")
+        super().reset()
         self.n = 0
 
     def feed(self, bank):
         """The last call's rows into an RdsClockBank or an RdsLinkBank, device to device.  Async on
         the context stream; call it once after each call."""
-        if bank.S != self.S:
-            raise ValueError(f"the bank has {bank.S} streams, the carrier stage {self.S}")
+        self._check_streams(bank, "bank", "carrier stage")
         bank.process_dev(self.rows_ptr, self.n, self.rows_stride)
 
     def clock(self, **kw) -> "RdsClockBank":

@@ -21,6 +21,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "rds_code.h"
 #include "sdr_ctx.h"
 
 // launchers implemented in fe.hip / fir.hip / pll.hip / psd.hip: sdr_launch.h;
@@ -1211,21 +1212,6 @@ struct sdr_rds_link {
   std::vector<uint8_t> prev_sync_bits;
 };
 
-namespace {
-// parity matrix H (26 x 10), model/fmRDSblock.py:49, one row per bit as 10-bit masks (bit i = column i)
-constexpr uint8_t kRdsH[26][10] = {
-    {1,0,0,0,0,0,0,0,0,0},{0,1,0,0,0,0,0,0,0,0},{0,0,1,0,0,0,0,0,0,0},{0,0,0,1,0,0,0,0,0,0},
-    {0,0,0,0,1,0,0,0,0,0},{0,0,0,0,0,1,0,0,0,0},{0,0,0,0,0,0,1,0,0,0},{0,0,0,0,0,0,0,1,0,0},
-    {0,0,0,0,0,0,0,0,1,0},{0,0,0,0,0,0,0,0,0,1},{1,0,1,1,0,1,1,1,0,0},{0,1,0,1,1,0,1,1,1,0},
-    {0,0,1,0,1,1,0,1,1,1},{1,0,1,0,0,0,0,1,1,1},{1,1,1,0,0,1,1,1,1,1},{1,1,0,0,0,1,0,0,1,1},
-    {1,1,0,1,0,1,0,1,0,1},{1,1,0,1,1,1,0,1,1,0},{0,1,1,0,1,1,1,0,1,1},{1,0,0,0,0,0,0,0,0,1},
-    {1,1,1,1,0,1,1,1,0,0},{0,1,1,1,1,0,1,1,1,0},{0,0,1,1,1,1,0,1,1,1},{1,0,1,0,1,0,0,1,1,1},
-    {1,1,1,0,0,0,1,1,1,1},{1,1,0,0,0,1,1,0,1,1}};
-// syndromes A, B, C, D (model/fmRDSblock.py:300, :307, :314, :321)
-constexpr uint8_t kRdsSyn[4][10] = {{1,1,1,1,0,1,1,0,0,0}, {1,1,1,1,0,1,0,1,0,0},
-                                    {1,0,0,1,0,1,1,1,0,0}, {1,0,0,1,0,1,1,0,0,0}};
-}  // namespace
-
 extern "C" {
 
 int sdr_rds_link_create(sdr_rds_link** out) {
@@ -1307,11 +1293,10 @@ int sdr_rds_link_block(sdr_rds_link* l, const double* rrc_i, int64_t n, int64_t*
   int64_t ne = 0;
   int64_t position = 0;
   for (;;) {                                                          // :299-341
-    uint8_t syn[10] = {0};
-    for (int i = 0; i < 10; ++i)
-      for (int j = 0; j < 26; ++j) syn[i] ^= (uint8_t)(d[position + j] & kRdsH[j][i]);
-    for (int typ = 0; typ < 4; ++typ) {
-      if (std::memcmp(syn, kRdsSyn[typ], 10) != 0) continue;
+    uint32_t pat = 0;                                                 // rds_code.h: the first bit is bit 25
+    for (int j = 0; j < 26; ++j) pat |= (uint32_t)(d[position + j] & 1u) << (25 - j);
+    const int typ = type_of(syndrome(pat));
+    if (typ < 4) {                                                    // A .. D (model/fmRDSblock.py:300-321)
       const int64_t pp = l->printposition;
       const bool ok = l->last_position == -1 || pp - l->last_position == 26;
       if (ok) l->last_position = pp;
@@ -1322,7 +1307,6 @@ int sdr_rds_link_block(sdr_rds_link* l, const double* rrc_i, int64_t n, int64_t*
       }
       ++ne;
       l->bad_sync = ok ? 0 : l->bad_sync + 1;
-      break;
     }
     if (l->resync_after > 0 && l->bad_sync > l->resync_after) {   // src/fm_radio.cpp:697-704
       if (events && ne < max_events) {

@@ -20,11 +20,13 @@
 //           rule itself a few scalar instructions per match), the events and the next state.
 // Everything a launch derives from the state (block 0 or not, offset, start position, counts)
 // is derived the same way by all three from `plan_of`, so they agree without a hand-off; the
-// frame launch is the only one that writes the state, and it runs last.
+// frame launch is the only one that writes the state, and it runs last.  The code -- H, the offset
+// syndromes, a window out of the LDS words, its information word -- is rds_code.h's.
 #include <hip/hip_runtime.h>
 
 #include <new>
 
+#include "rds_code.h"
 #include "rds_links.h"
 #include "sdr_ctx.h"
 
@@ -35,40 +37,10 @@ namespace {
 constexpr int RDS_T = 256, RDS_TILE = 256, RDS_NW = RDS_T / 64, RDS_SPS = 24;
 static_assert(RDS_TILE == RDS_T, "one position of the scanned row per thread");
 
-// parity matrix H (26 x 10) and syndromes A..D, model/fmRDSblock.py:49, :300-321 (as capi.hip)
-constexpr uint8_t kH[26][10] = {
-    {1,0,0,0,0,0,0,0,0,0},{0,1,0,0,0,0,0,0,0,0},{0,0,1,0,0,0,0,0,0,0},{0,0,0,1,0,0,0,0,0,0},
-    {0,0,0,0,1,0,0,0,0,0},{0,0,0,0,0,1,0,0,0,0},{0,0,0,0,0,0,1,0,0,0},{0,0,0,0,0,0,0,1,0,0},
-    {0,0,0,0,0,0,0,0,1,0},{0,0,0,0,0,0,0,0,0,1},{1,0,1,1,0,1,1,1,0,0},{0,1,0,1,1,0,1,1,1,0},
-    {0,0,1,0,1,1,0,1,1,1},{1,0,1,0,0,0,0,1,1,1},{1,1,1,0,0,1,1,1,1,1},{1,1,0,0,0,1,0,0,1,1},
-    {1,1,0,1,0,1,0,1,0,1},{1,1,0,1,1,1,0,1,1,0},{0,1,1,0,1,1,1,0,1,1},{1,0,0,0,0,0,0,0,0,1},
-    {1,1,1,1,0,1,1,1,0,0},{0,1,1,1,1,0,1,1,1,0},{0,0,1,1,1,1,0,1,1,1},{1,0,1,0,1,0,0,1,1,1},
-    {1,1,1,0,0,0,1,1,1,1},{1,1,0,0,0,1,1,0,1,1}};
-constexpr uint8_t kSyn[4][10] = {{1,1,1,1,0,1,1,0,0,0}, {1,1,1,1,0,1,0,1,0,0},
-                                 {1,0,0,1,0,1,1,1,0,0}, {1,0,0,1,0,1,1,0,0,0}};
-// column c of H as a mask over the window word (bit j = the window's bit j), and the syndromes
-// as 10-bit words (bit c = column c)
-constexpr uint32_t col_mask(int c) {
-  uint32_t m = 0;
-  for (int j = 0; j < 26; ++j) m |= (uint32_t)kH[j][c] << j;
-  return m;
-}
-constexpr uint32_t syn_word(int t) {
-  uint32_t m = 0;
-  for (int c = 0; c < 10; ++c) m |= (uint32_t)kSyn[t][c] << c;
-  return m;
-}
-template <int C>
-__device__ __forceinline__ uint32_t parity_col(uint32_t v) {
-  constexpr uint32_t m = col_mask(C);
-  return (uint32_t)(__popc(v & m) & 1) << C;
-}
-// the window's syndrome type 0..3, or -1
+// the window's syndrome type 0..3 (A..D), or -1: this layer does not know C'
 __device__ __forceinline__ int syndrome_type(uint32_t v) {
-  const uint32_t s = parity_col<0>(v) | parity_col<1>(v) | parity_col<2>(v) | parity_col<3>(v) | parity_col<4>(v) |
-                     parity_col<5>(v) | parity_col<6>(v) | parity_col<7>(v) | parity_col<8>(v) | parity_col<9>(v);
-  constexpr uint32_t sa = syn_word(0), sb = syn_word(1), sc = syn_word(2), sd = syn_word(3);
-  return s == sa ? 0 : s == sb ? 1 : s == sc ? 2 : s == sd ? 3 : -1;
+  const uint32_t s = syndrome_of(v);
+  return s == SYN_A ? 0 : s == SYN_B ? 1 : s == SYN_C ? 2 : s == SYN_D ? 3 : -1;
 }
 
 // a stream's carried state; all zero = "block 0 has not run" (load_state gives the start values)
@@ -247,9 +219,7 @@ __global__ __launch_bounds__(RDS_T) void rds_scan_kernel(const RdsArgs a) {
   int typ = -1;
   uint32_t v = 0;
   if (i < p.W) {
-    const int q = tid >> 5, r = tid & 31;
-    const unsigned long long pair = ((unsigned long long)dw[q + 1] << 32) | dw[q];
-    v = (uint32_t)(pair >> r) & 0x3ffffffu;
+    v = window_at(dw, tid);
     typ = syndrome_type(v);
   }
   const unsigned long long mm = __ballot(typ >= 0);
@@ -264,10 +234,8 @@ __global__ __launch_bounds__(RDS_T) void rds_scan_kernel(const RdsArgs a) {
   }
   if (typ >= 0) {
     const int rank = base + __popcll(mm & ((1ull << lane) - 1ull));
-    // information word: the window's first 16 bits, the first one most significant
-    const uint32_t word = __brev(v) >> 16;
     a.rec[(int64_t)s * a.tiles_stride * RDS_TILE + (int64_t)blockIdx.x * RDS_TILE + rank] =
-        ((uint32_t)tid << 18) | ((uint32_t)typ << 16) | word;
+        ((uint32_t)tid << 18) | ((uint32_t)typ << 16) | info_word(v);
   }
   if (tid == 0) a.tcount[(int64_t)s * a.tiles_stride + blockIdx.x] = total;
 }
@@ -453,6 +421,7 @@ struct sdr_rds_links {
   int64_t* ev = nullptr;
   int64_t* nev = nullptr;
   int* status = nullptr;
+  DevMem mem;
 };
 
 namespace {
@@ -460,17 +429,6 @@ namespace {
 // the most symbols, bits and scanned bits a row of n samples gives (offset 0; 27 carried bits)
 int64_t max_symbols(int64_t n) { return (n + RDS_SPS - 1) / RDS_SPS; }
 int64_t max_scanned(int64_t n) { return 27 + max_symbols(n) / 2; }
-
-int clear_outputs(sdr_rds_links* l) {
-  hipStream_t st = l->ctx->stream;
-  HIP_TRY(hipMemsetAsync(l->state, 0, sizeof(RdsState) * l->S, st));
-  HIP_TRY(hipMemsetAsync(l->cnt, 0, sizeof(unsigned) * 2 * l->S, st));
-  HIP_TRY(hipMemsetAsync(l->nbd, 0, sizeof(int) * 2 * l->S, st));
-  HIP_TRY(hipMemsetAsync(l->added, 0, sizeof(int) * 2 * l->S, st));
-  HIP_TRY(hipMemsetAsync(l->nev, 0, sizeof(int64_t) * l->S, st));
-  HIP_TRY(hipMemsetAsync(l->status, 0, sizeof(int) * l->S, st));
-  return SDR_OK;
-}
 
 }  // namespace
 
@@ -505,27 +463,25 @@ int sdr_rds_links_create(sdr_ctx* c, int nstreams, int64_t max_n, int64_t max_ev
   l->diff_stride = (max_scanned(max_n) + 15) / 16 * 16;
   l->tiles_stride = ceil_div(max_scanned(max_n), RDS_TILE);
   const size_t S = (size_t)nstreams;
-  hipError_t e = hipMalloc(&l->state, sizeof(RdsState) * S);
-  if (e == hipSuccess) e = hipMalloc(&l->sym, sizeof(float) * S * l->sym_stride);
-  if (e == hipSuccess) e = hipMalloc(&l->bits, S * l->bits_stride);
-  if (e == hipSuccess) e = hipMalloc(&l->diff, S * l->diff_stride);
-  if (e == hipSuccess) e = hipMalloc(&l->cnt, sizeof(unsigned) * 2 * S);
-  if (e == hipSuccess) e = hipMalloc(&l->tcount, sizeof(int) * S * l->tiles_stride);
-  if (e == hipSuccess) e = hipMalloc(&l->rec, sizeof(uint32_t) * S * l->tiles_stride * RDS_TILE);
-  if (e == hipSuccess) e = hipMalloc(&l->cm, sizeof(uint2) * S * l->tiles_stride * RDS_TILE);
-  if (e == hipSuccess) e = hipMalloc(&l->nbd, sizeof(int) * 2 * S);
-  if (e == hipSuccess) e = hipMalloc(&l->added, sizeof(int) * 2 * S);
-  if (e == hipSuccess) e = hipMalloc(&l->ev, sizeof(int64_t) * 4 * S * (size_t)max_events);
-  if (e == hipSuccess) e = hipMalloc(&l->nev, sizeof(int64_t) * S);
-  if (e == hipSuccess) e = hipMalloc(&l->status, sizeof(int) * S);
-  if (e != hipSuccess) {
+  DevMem& m = l->mem;             // `true`: what a reset clears
+  m.get(&l->state, S, true);
+  m.get(&l->sym, S * l->sym_stride);
+  m.get(&l->bits, S * l->bits_stride);
+  m.get(&l->diff, S * l->diff_stride);
+  m.get(&l->cnt, 2 * S, true);
+  m.get(&l->tcount, S * l->tiles_stride);
+  m.get(&l->rec, S * l->tiles_stride * RDS_TILE);
+  m.get(&l->cm, S * l->tiles_stride * RDS_TILE);
+  m.get(&l->nbd, 2 * S, true);
+  m.get(&l->added, 2 * S, true);
+  m.get(&l->ev, 4 * S * (size_t)max_events);
+  m.get(&l->nev, S, true);
+  m.get(&l->status, S, true);
+  if (m.err == hipSuccess) m.err = m.zero(c->stream);
+  if (m.err != hipSuccess) {
+    const hipError_t e = m.err;
     sdr_rds_links_destroy(l);
-    return fail(e == hipErrorOutOfMemory ? SDR_ENOMEM : SDR_EHIP, "sdr_rds_links_create: %s", hipGetErrorString(e));
-  }
-  const int rc = clear_outputs(l);
-  if (rc != SDR_OK) {
-    sdr_rds_links_destroy(l);
-    return rc;
+    return create_failed(e, "sdr_rds_links_create");
   }
   *out = l;
   return SDR_OK;
@@ -534,19 +490,7 @@ int sdr_rds_links_create(sdr_ctx* c, int nstreams, int64_t max_n, int64_t max_ev
 void sdr_rds_links_destroy(sdr_rds_links* l) {
   if (l == nullptr) return;
   if (l->ctx != nullptr && set_dev(l->ctx) == SDR_OK) (void)hipStreamSynchronize(l->ctx->stream);
-  (void)hipFree(l->state);
-  (void)hipFree(l->sym);
-  (void)hipFree(l->bits);
-  (void)hipFree(l->diff);
-  (void)hipFree(l->cnt);
-  (void)hipFree(l->tcount);
-  (void)hipFree(l->rec);
-  (void)hipFree(l->cm);
-  (void)hipFree(l->nbd);
-  (void)hipFree(l->added);
-  (void)hipFree(l->ev);
-  (void)hipFree(l->nev);
-  (void)hipFree(l->status);
+  l->mem.release();
   delete l;
 }
 
@@ -559,7 +503,8 @@ int sdr_rds_links_set_resync(sdr_rds_links* l, int after_bad_syncs) {
 int sdr_rds_links_reset(sdr_rds_links* l) {
   if (l == nullptr) return fail(SDR_EINVAL, "sdr_rds_links_reset: object is NULL");
   TRY(set_dev(l->ctx));
-  return clear_outputs(l);
+  HIP_TRY(l->mem.zero(l->ctx->stream));
+  return SDR_OK;
 }
 
 int sdr_rds_links_process_dev(sdr_rds_links* l, const float* rrc_i, int64_t n, int64_t stride) {

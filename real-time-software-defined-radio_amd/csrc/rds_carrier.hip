@@ -26,19 +26,20 @@
 //           others; the last n mod 4 samples of a row one by one.
 //   finish  the carried samples and the last 16 moment triples of (the carried ones, the call's)
 //           into the other of two slots (a call reads one and fills the other).
+// The segment geometry, the host's cursor, the rows across the seam, the window that reaches into
+// the carried triples and the chunks are rds_seg.h's, shared with rds_clock.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <new>
 
-#include "sdr_ctx.h"
+#include "rds_seg.h"
 
 using namespace sdrint;
 
 namespace {
 
-constexpr int SPS = 24, SEG_SYM = 32, SEG = SPS * SEG_SYM;
 constexpr int CR_T = 256;
 constexpr int CR_MSEG = CR_T / SPS;            // segments of a moments workgroup: 10 (240 lanes)
 constexpr int CR_KEEP = SDR_RDS_CARRIER_MAX_WINDOW;        // carried moment triples in front of a call
@@ -60,9 +61,7 @@ struct CarrierState {
 };
 
 struct CarrierArgs {
-  const float* xi; const float* xq; int64_t n, stride;
-  int64_t seg0;                 // complete segments before this call
-  int G, tail;                  // the call's complete segments; the carried samples
+  const float* xi; const float* xq; SegCall c;
   int window;
   int64_t gstride, kstride;     // complete segments / segments per stream of the per-call arrays
   int64_t ystride;
@@ -76,13 +75,14 @@ struct CarrierArgs {
   float* y;                     // [stream][ystride]
 };
 
-// sample v of one of the call's rows, 0 <= v < tail + n
-struct CarrierRow {
-  const float* x; const float* carry; int tail;
-  __device__ __forceinline__ float operator()(int64_t v) const { return v < tail ? carry[v] : x[v - tail]; }
-};
+// the call's row q (0: i, 1: q) of stream s; its moment triples, the carried ones in front
+using CarrierRow = SegRow<0>;
+using MomentWindow = SegWindow<double, 3, CR_KEEP>;
 __device__ __forceinline__ CarrierRow row_of(const CarrierArgs& a, int s, int q) {
-  return CarrierRow{(q ? a.xq : a.xi) + (int64_t)s * a.stride, a.carry_in + ((int64_t)s * 2 + q) * SEG, a.tail};
+  return CarrierRow{(q ? a.xq : a.xi) + (int64_t)s * a.c.stride, a.carry_in + ((int64_t)s * 2 + q) * SEG, a.c.tail};
+}
+__device__ __forceinline__ MomentWindow moments_of(const CarrierArgs& a, int s) {
+  return MomentWindow{a.M + (int64_t)s * a.gstride * 3, a.mcar_in + (int64_t)s * CR_KEEP * 3};
 }
 
 __global__ __launch_bounds__(CR_T) void rds_carrier_moments_kernel(const CarrierArgs a) {
@@ -91,32 +91,14 @@ __global__ __launch_bounds__(CR_T) void rds_carrier_moments_kernel(const Carrier
   const int g = blockIdx.x * CR_MSEG + tid / SPS, p = tid % SPS;
   if (tid < CR_MSEG * SPS) {
     double eii = 0.0, eqq = 0.0, eiq = 0.0;
-    if (g < a.G) {
-      const CarrierRow ri = row_of(a, s, 0), rq = row_of(a, s, 1);
-      const int64_t v0 = (int64_t)g * SEG + p;
-      if (v0 - p >= a.tail) {                   // the whole segment lies in the caller's rows
-        const float* __restrict__ xi = ri.x + (v0 - a.tail);
-        const float* __restrict__ xq = rq.x + (v0 - a.tail);
-#pragma unroll 8
-        for (int j = 0; j < SEG_SYM; ++j) {
-          const float fi = xi[SPS * j], fq = xq[SPS * j];
-          const bool ok = __builtin_isfinite(fi) && __builtin_isfinite(fq);
-          const double di = ok ? (double)fi : 0.0, dq = ok ? (double)fq : 0.0;
-          eii += di * di;
-          eqq += dq * dq;
-          eiq += di * dq;
-        }
-      } else {
-        for (int j = 0; j < SEG_SYM; ++j) {
-          const float fi = ri(v0 + SPS * j), fq = rq(v0 + SPS * j);
-          const bool ok = __builtin_isfinite(fi) && __builtin_isfinite(fq);
-          const double di = ok ? (double)fi : 0.0, dq = ok ? (double)fq : 0.0;
-          eii += di * di;
-          eqq += dq * dq;
-          eiq += di * dq;
-        }
-      }
-    }
+    if (g < a.c.G)
+      seg_samples(g, p, a.c.tail, [&](float fi, float fq) {
+        const bool ok = __builtin_isfinite(fi) && __builtin_isfinite(fq);
+        const double di = ok ? (double)fi : 0.0, dq = ok ? (double)fq : 0.0;
+        eii += di * di;
+        eqq += dq * dq;
+        eiq += di * dq;
+      }, row_of(a, s, 0), row_of(a, s, 1));
     part[0][tid] = eii;
     part[1][tid] = eqq;
     part[2][tid] = eiq;
@@ -124,7 +106,7 @@ __global__ __launch_bounds__(CR_T) void rds_carrier_moments_kernel(const Carrier
   __syncthreads();
   if (tid < 3 * CR_MSEG) {
     const int gl = tid / 3, k = tid % 3, gs = blockIdx.x * CR_MSEG + gl;
-    if (gs < a.G) {
+    if (gs < a.c.G) {
       double t = 0.0;
       for (int q = 0; q < SPS; ++q) t += part[k][gl * SPS + q];
       a.M[((int64_t)s * a.gstride + gs) * 3 + k] = t;
@@ -164,17 +146,16 @@ __device__ __forceinline__ int map_apply(const uint8_t* f, int kappa) { return f
 __global__ __launch_bounds__(TR_T) void rds_carrier_track_kernel(const CarrierArgs a) {
   __shared__ uint8_t maps[2][TR_CH][32];
   __shared__ int red[2][TR_T / 64];
-  const int s = blockIdx.x, tid = threadIdx.x, G = a.G, N = a.G + 1;
+  const int s = blockIdx.x, tid = threadIdx.x, G = a.c.G, N = G + 1;
   CarrierState* st = a.state + s;
   const int seed = st->kappa;
   int* info = a.info + (int64_t)s * a.kstride;       // both are read where other threads have written
   uint8_t* tab = a.ptab + (int64_t)s * a.kstride * 32;
-  const double* __restrict__ M = a.M + (int64_t)s * a.gstride * 3;
-  const double* __restrict__ mcar = a.mcar_in + (int64_t)s * CR_KEEP * 3;
+  const MomentWindow moments = moments_of(a, s);
 
   // the code of every segment: the window's triples, oldest first
   for (int g = tid; g < N; g += TR_T) {
-    const int64_t gabs = a.seg0 + g;
+    const int64_t gabs = a.c.seg0 + g;
     int code = C_NONE;                          // segment 0
     if (gabs >= 1) {
       const int w = gabs < a.window ? (int)gabs : a.window;
@@ -184,7 +165,7 @@ __global__ __launch_bounds__(TR_T) void rds_carrier_track_kernel(const CarrierAr
 #pragma unroll 8
       for (int k = CR_KEEP; k >= 1; --k) {
         const int gl = g - k;                   // >= -CR_KEEP
-        const double* __restrict__ m = gl >= 0 ? M + (int64_t)gl * 3 : mcar + (CR_KEEP + gl) * 3;
+        const double* __restrict__ m = moments.at(gl);
         const double m0 = m[0], m1 = m[1], m2 = m[2];
         if (k <= w) {
           A += m0;
@@ -206,9 +187,9 @@ __global__ __launch_bounds__(TR_T) void rds_carrier_track_kernel(const CarrierAr
 
   // 32 lanes walk a chunk of segments, lane v from kappa = v: tab[g][v] = where the chunk's segments
   // up to g take v, and the last of them is the chunk's map
-  const int C = (N + TR_CH - 1) / TR_CH;
   const int c = tid >> 5, v = tid & 31;
-  const int g_lo = c * C < N ? c * C : N, g_hi = g_lo + C < N ? g_lo + C : N;
+  const SegChunk ch = chunk_of(c, N, TR_CH);
+  const int C = ch.C, g_lo = ch.lo, g_hi = ch.hi, nact = ch.nact;
   {
     int m = v;
     for (int g = g_lo; g < g_hi; g += 8) {      // eight codes in flight: a store may not pass a load
@@ -223,7 +204,6 @@ __global__ __launch_bounds__(TR_T) void rds_carrier_track_kernel(const CarrierAr
     }
     maps[0][c][v] = (uint8_t)m;
   }
-  const int nact = (N + C - 1) / C;             // chunks that are not empty
   int cur = 0;
   for (int off = 1; off < nact; off <<= 1) {    // inclusive scan: chunks 0 .. c in order
     __syncthreads();
@@ -298,16 +278,16 @@ __device__ __forceinline__ vec4f load4(const float* __restrict__ p) {
 __global__ __launch_bounds__(CR_T) void rds_carrier_rotate_kernel(const CarrierArgs a) {
   const int s = blockIdx.y;
   const int64_t v = ((int64_t)blockIdx.x * CR_T + threadIdx.x) * 4;
-  if (v >= a.n) return;
-  const float* __restrict__ xi = a.xi + (int64_t)s * a.stride + v;
-  const float* __restrict__ xq = a.xq + (int64_t)s * a.stride + v;
+  if (v >= a.c.n) return;
+  const float* __restrict__ xi = a.xi + (int64_t)s * a.c.stride + v;
+  const float* __restrict__ xq = a.xq + (int64_t)s * a.c.stride + v;
   float* __restrict__ y = a.y + (int64_t)s * a.ystride + v;
   const int* __restrict__ info = a.info + (int64_t)s * a.kstride;
-  const int64_t r = a.tail + v;                 // the sample's place in the call's row
+  const int64_t r = a.c.tail + v;               // the sample's place in the call's row
   const int g0 = (int)(r / SEG);                // <= G
   const float2 ax0 = a.axes[info[g0] & 63];
   const float c0 = ax0.x, s0 = ax0.y;
-  if (v + 4 <= a.n) {
+  if (v + 4 <= a.c.n) {
     const int64_t edge = (int64_t)(g0 + 1) * SEG - r;             // the samples of this thread in g0
     float c1 = c0, s1 = s0;
     if (edge < 4) {
@@ -323,7 +303,7 @@ __global__ __launch_bounds__(CR_T) void rds_carrier_rotate_kernel(const CarrierA
     o.w = project(edge > 3 ? c0 : c1, edge > 3 ? s0 : s1, fi.w, fq.w);
     *reinterpret_cast<vec4f*>(y) = o;           // the bank's rows: 16-byte aligned, v a multiple of 4
   } else {
-    const int left = (int)(a.n - v);            // 1 .. 3
+    const int left = (int)(a.c.n - v);          // 1 .. 3
     for (int k = 0; k < left; ++k) {
       float c1 = c0, s1 = s0;
       if ((r + k) / SEG != g0) {
@@ -340,18 +320,14 @@ __global__ __launch_bounds__(CR_T) void rds_carrier_finish_kernel(const CarrierA
   const int s = blockIdx.y;
   const int64_t i = (int64_t)blockIdx.x * CR_T + threadIdx.x;
   // the next call's carried samples: those of the unfinished segment
-  const int G = a.G;
-  const int64_t L = a.tail + a.n - (int64_t)G * SEG;              // < 768
+  const int G = a.c.G;
+  const int64_t L = a.c.tail + a.c.n - (int64_t)G * SEG;          // < 768
   if (i < L) {
     a.carry_out[((int64_t)s * 2 + 0) * SEG + i] = row_of(a, s, 0)((int64_t)G * SEG + i);
     a.carry_out[((int64_t)s * 2 + 1) * SEG + i] = row_of(a, s, 1)((int64_t)G * SEG + i);
   }
   // ... and the last CR_KEEP moment triples of (the carried ones, the call's)
-  if (i < CR_KEEP * 3) {
-    const int gl = G - CR_KEEP + (int)i / 3, k = (int)i % 3;
-    a.mcar_out[(int64_t)s * CR_KEEP * 3 + i] = gl >= 0 ? a.M[((int64_t)s * a.gstride + gl) * 3 + k]
-                                                        : a.mcar_in[((int64_t)s * CR_KEEP + CR_KEEP + gl) * 3 + k];
-  }
+  if (i < CR_KEEP * 3) a.mcar_out[(int64_t)s * CR_KEEP * 3 + i] = moments_of(a, s).roll(G, (int)i);
 }
 
 // the axis table: entries 0 .. 8 rounded from f64, the rest by symmetry; no negative zeros
@@ -384,9 +360,8 @@ struct sdr_rds_carrier {
   sdr_ctx* ctx = nullptr;
   int S = 0, window = 8;
   int64_t max_n = 0, gstride = 0, kstride = 0, ystride = 0;
-  // host-side: every stream of a call brings the same n
-  int64_t consumed = 0, seg0 = 0;
-  int tail = 0, cur = 0;
+  SegCursor seg;
+  DevMem mem;
   float axes_host[2 * CR_NK] = {};
   float* carry[2] = {nullptr, nullptr};
   double* mcar[2] = {nullptr, nullptr};
@@ -397,25 +372,6 @@ struct sdr_rds_carrier {
   float2* axes = nullptr;
   float* y = nullptr;
 };
-
-namespace {
-
-size_t carry_bytes(const sdr_rds_carrier* k) { return sizeof(float) * 2 * SEG * (size_t)k->S; }
-size_t mcar_bytes(const sdr_rds_carrier* k) { return sizeof(double) * CR_KEEP * 3 * (size_t)k->S; }
-
-int clear_carrier(sdr_rds_carrier* k) {
-  hipStream_t st = k->ctx->stream;
-  for (int q = 0; q < 2; ++q) {
-    HIP_TRY(hipMemsetAsync(k->carry[q], 0, carry_bytes(k), st));
-    HIP_TRY(hipMemsetAsync(k->mcar[q], 0, mcar_bytes(k), st));
-  }
-  HIP_TRY(hipMemsetAsync(k->state, 0, sizeof(CarrierState) * k->S, st));
-  k->consumed = k->seg0 = 0;
-  k->tail = k->cur = 0;
-  return SDR_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -438,29 +394,24 @@ int sdr_rds_carrier_create(sdr_ctx* c, int nstreams, int64_t max_n, sdr_rds_carr
   k->ystride = ceil_div(max_n, 64) * 64;
   build_axes(k->axes_host);
   const size_t S = (size_t)nstreams;
-  hipError_t e = hipSuccess;
-  for (int q = 0; q < 2 && e == hipSuccess; ++q) {
-    e = hipMalloc(&k->carry[q], carry_bytes(k));
-    if (e == hipSuccess) e = hipMalloc(&k->mcar[q], mcar_bytes(k));
-  }
-  if (e == hipSuccess) e = hipMalloc(&k->state, sizeof(CarrierState) * S);
-  if (e == hipSuccess) e = hipMalloc(&k->M, sizeof(double) * 3 * S * (size_t)k->gstride);
-  if (e == hipSuccess) e = hipMalloc(&k->info, sizeof(int) * S * (size_t)k->kstride);
-  if (e == hipSuccess) e = hipMalloc(&k->ptab, 32 * S * (size_t)k->kstride);
-  if (e == hipSuccess) e = hipMalloc(&k->y, sizeof(float) * S * (size_t)k->ystride);
-  if (e == hipSuccess) e = hipMalloc(&k->axes, sizeof(float) * 2 * CR_NK);
+  DevMem& m = k->mem;             // `true`: what a reset clears
+  m.get2(k->carry, 2 * SEG * S, true);
+  m.get2(k->mcar, CR_KEEP * 3 * S, true);
+  m.get(&k->state, S, true);
+  m.get(&k->M, 3 * S * (size_t)k->gstride);
+  m.get(&k->info, S * (size_t)k->kstride);
+  m.get(&k->ptab, 32 * S * (size_t)k->kstride);
+  m.get(&k->y, S * (size_t)k->ystride);
+  m.get(&k->axes, CR_NK);
+  hipError_t e = m.err;
   if (e == hipSuccess) e = hipMemcpyAsync(k->axes, k->axes_host, sizeof(float) * 2 * CR_NK, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipMemsetAsync(k->info, 0, sizeof(int) * S * (size_t)k->kstride, c->stream);
   if (e == hipSuccess) e = hipMemsetAsync(k->y, 0, sizeof(float) * S * (size_t)k->ystride, c->stream);
+  if (e == hipSuccess) e = m.zero(c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);       // axes_host has been read
   if (e != hipSuccess) {
     sdr_rds_carrier_destroy(k);
     return create_failed(e, "sdr_rds_carrier_create");
-  }
-  const int rc = clear_carrier(k);
-  if (rc != SDR_OK) {
-    sdr_rds_carrier_destroy(k);
-    return rc;
   }
   *out = k;
   return SDR_OK;
@@ -469,23 +420,16 @@ int sdr_rds_carrier_create(sdr_ctx* c, int nstreams, int64_t max_n, sdr_rds_carr
 void sdr_rds_carrier_destroy(sdr_rds_carrier* k) {
   if (k == nullptr) return;
   if (k->ctx != nullptr && set_dev(k->ctx) == SDR_OK) (void)hipStreamSynchronize(k->ctx->stream);
-  for (int q = 0; q < 2; ++q) {
-    (void)hipFree(k->carry[q]);
-    (void)hipFree(k->mcar[q]);
-  }
-  (void)hipFree(k->state);
-  (void)hipFree(k->M);
-  (void)hipFree(k->info);
-  (void)hipFree(k->ptab);
-  (void)hipFree(k->y);
-  (void)hipFree(k->axes);
+  k->mem.release();
   delete k;
 }
 
 int sdr_rds_carrier_reset(sdr_rds_carrier* k) {
   if (k == nullptr) return fail(SDR_EINVAL, "sdr_rds_carrier_reset: object is NULL");
   TRY(set_dev(k->ctx));
-  return clear_carrier(k);
+  HIP_TRY(k->mem.zero(k->ctx->stream));
+  k->seg = SegCursor{};
+  return SDR_OK;
 }
 
 int sdr_rds_carrier_set_params(sdr_rds_carrier* k, int window) {
@@ -497,32 +441,22 @@ int sdr_rds_carrier_set_params(sdr_rds_carrier* k, int window) {
 }
 
 int sdr_rds_carrier_process_dev(sdr_rds_carrier* k, const float* rrc_i, const float* rrc_q, int64_t n, int64_t stride) {
-  if (k == nullptr) return fail(SDR_EINVAL, "sdr_rds_carrier_process_dev: object is NULL");
-  if (rrc_i == nullptr || rrc_q == nullptr) return fail(SDR_EINVAL, "sdr_rds_carrier_process_dev: rrc_i or rrc_q is NULL");
-  if (n < 0 || n > k->max_n)
-    return fail(SDR_EINVAL, "sdr_rds_carrier_process_dev: n=%lld outside [0, max_n=%lld]", (long long)n, (long long)k->max_n);
-  if (stride < n) return fail(SDR_EINVAL, "sdr_rds_carrier_process_dev: stride=%lld < n=%lld", (long long)stride, (long long)n);
-  if ((((uintptr_t)rrc_i | (uintptr_t)rrc_q) & 3) != 0)
-    return fail(SDR_EINVAL, "sdr_rds_carrier_process_dev: rrc_i and rrc_q must be aligned to 4 B");
+  TRY(seg_check_call(k, {rrc_i, rrc_q}, n, stride, "sdr_rds_carrier_process_dev"));
   sdr_ctx* c = k->ctx;
   TRY(set_dev(c));
-  const int64_t G = (k->tail + n) / SEG;        // <= gstride: tail <= 767
   CarrierArgs a;
   a.xi = rrc_i;
   a.xq = rrc_q;
-  a.n = n;
-  a.stride = stride;
-  a.seg0 = k->seg0;
-  a.G = (int)G;
-  a.tail = k->tail;
+  a.c = k->seg.begin(n, stride);
+  const int64_t G = a.c.G;                      // <= gstride: tail <= 767
   a.window = k->window;
   a.gstride = k->gstride;
   a.kstride = k->kstride;
   a.ystride = k->ystride;
-  a.carry_in = k->carry[k->cur];
-  a.carry_out = k->carry[k->cur ^ 1];
-  a.mcar_in = k->mcar[k->cur];
-  a.mcar_out = k->mcar[k->cur ^ 1];
+  a.carry_in = k->carry[k->seg.cur];
+  a.carry_out = k->carry[k->seg.cur ^ 1];
+  a.mcar_in = k->mcar[k->seg.cur];
+  a.mcar_out = k->mcar[k->seg.cur ^ 1];
   a.state = k->state;
   a.M = k->M;
   a.info = k->info;
@@ -535,10 +469,7 @@ int sdr_rds_carrier_process_dev(sdr_rds_carrier* k, const float* rrc_i, const fl
   hipLaunchKernelGGL(rds_carrier_rotate_kernel, dim3((unsigned)std::max<int64_t>(1, ceil_div(n, 4 * CR_T)), S), dim3(CR_T), 0, c->stream, a);
   hipLaunchKernelGGL(rds_carrier_finish_kernel, dim3((unsigned)ceil_div(SEG, CR_T), S), dim3(CR_T), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
-  k->cur ^= 1;
-  k->tail = (int)(k->tail + n - G * SEG);
-  k->seg0 += G;
-  k->consumed += n;
+  k->seg.commit(a.c);
   return SDR_OK;
 }
 
@@ -566,15 +497,12 @@ int sdr_rds_carrier_fetch(sdr_rds_carrier* k, float* rows, int64_t n) {
 int sdr_rds_carrier_state(sdr_rds_carrier* k, int64_t* state) {
   if (k == nullptr) return fail(SDR_EINVAL, "sdr_rds_carrier_state: object is NULL");
   if (state == nullptr) return fail(SDR_EINVAL, "sdr_rds_carrier_state: state is NULL");
-  sdr_ctx* c = k->ctx;
-  TRY(set_dev(c));
-  std::vector<CarrierState> st((size_t)k->S);
-  HIP_TRY(hipMemcpyAsync(st.data(), k->state, sizeof(CarrierState) * st.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  std::vector<CarrierState> st;
+  TRY(fetch_states(k->ctx, k->state, k->S, &st));
   for (int s = 0; s < k->S; ++s) {
     int64_t* o = state + (size_t)SDR_RDS_CARRIER_NSTATE * s;
-    o[0] = k->consumed;
-    o[1] = k->seg0;
+    o[0] = k->seg.seg0 * SEG + k->seg.tail;
+    o[1] = k->seg.seg0;
     o[2] = st[s].kappa;
     o[3] = st[s].fwd;
     o[4] = st[s].back;
@@ -587,11 +515,8 @@ int sdr_rds_carrier_state(sdr_rds_carrier* k, int64_t* state) {
 int sdr_rds_carrier_moments(sdr_rds_carrier* k, double* abc) {
   if (k == nullptr) return fail(SDR_EINVAL, "sdr_rds_carrier_moments: object is NULL");
   if (abc == nullptr) return fail(SDR_EINVAL, "sdr_rds_carrier_moments: abc is NULL");
-  sdr_ctx* c = k->ctx;
-  TRY(set_dev(c));
-  std::vector<CarrierState> st((size_t)k->S);
-  HIP_TRY(hipMemcpyAsync(st.data(), k->state, sizeof(CarrierState) * st.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  std::vector<CarrierState> st;
+  TRY(fetch_states(k->ctx, k->state, k->S, &st));
   for (int s = 0; s < k->S; ++s) {
     abc[3 * s] = st[s].A;
     abc[3 * s + 1] = st[s].B;

@@ -24,18 +24,19 @@
 //           store a byte at the pair's bit index.
 //   finish  diff = bit xor the bit before it; the counts; the carried samples, energy vectors and
 //           sign-change counts into the other of two slots (a call reads one and fills the other).
+// The segment geometry, the host's cursor, the row across the seam, the windows that reach into the
+// carried vectors and counts, the chunks and their scan are rds_seg.h's, shared with rds_carrier.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <new>
 
-#include "sdr_ctx.h"
+#include "rds_seg.h"
 
 using namespace sdrint;
 
 namespace {
 
-constexpr int SPS = 24, SEG_SYM = 32, SEG = SPS * SEG_SYM;
 constexpr int CK_T = 256, CK_NW = CK_T / 64;
 constexpr int CK_ESEG = CK_T / SPS;            // segments of an energy workgroup: 10 (240 lanes)
 constexpr int CK_KEEP = SDR_RDS_CLOCK_MAX_WINDOW - 1;      // carried vectors in front of a call
@@ -57,9 +58,7 @@ struct ClockCall {
 };
 
 struct ClockArgs {
-  const float* x; int64_t n, stride;
-  int64_t seg0;                 // segments done before this call
-  int G, tail;                  // the call's complete segments; the carried samples behind the 24
+  const float* x; SegCall c;    // c.tail: the carried samples behind the 24
   int window, hysteresis;
   int64_t gstride;              // segments per stream of the per-call arrays
   int64_t max_bits, bit_stride, diff_stride;
@@ -73,13 +72,19 @@ struct ClockArgs {
   uint8_t* diff; int* counts;
 };
 
-// sample v of the call's row, -24 <= v < tail + n
-struct ClockRow {
-  const float* x; const float* carry; int tail;
-  __device__ __forceinline__ float operator()(int64_t v) const { return v < tail ? carry[SPS + v] : x[v - tail]; }
-};
+// the call's row of stream s, from the 24 samples before its first segment on; its energy vectors
+// and sign-change counts, the carried ones in front
+using ClockRow = SegRow<SPS>;
+using EnergyWindow = SegWindow<double, SPS, CK_KEEP>;
+using CountWindow = SegWindow<int, 2, CK_KEEP>;
 __device__ __forceinline__ ClockRow row_of(const ClockArgs& a, int s) {
-  return ClockRow{a.x + (int64_t)s * a.stride, a.carry_in + (int64_t)s * CK_CARRY, a.tail};
+  return ClockRow{a.x + (int64_t)s * a.c.stride, a.carry_in + (int64_t)s * CK_CARRY, a.c.tail};
+}
+__device__ __forceinline__ EnergyWindow energy_of(const ClockArgs& a, int s) {
+  return EnergyWindow{a.E + (int64_t)s * a.gstride * SPS, a.ecar_in + (int64_t)s * CK_KEEP * SPS};
+}
+__device__ __forceinline__ CountWindow counts_of(const ClockArgs& a, int s) {
+  return CountWindow{a.cc + (int64_t)s * a.gstride * 2, a.ccar_in + (int64_t)s * CK_KEEP * 2};
 }
 
 __device__ __forceinline__ int step_phi(int phi, int phat) {
@@ -91,41 +96,13 @@ __device__ __forceinline__ int step_phi(int phi, int phat) {
 __global__ __launch_bounds__(CK_T) void rds_clock_energy_kernel(const ClockArgs a) {
   const int s = blockIdx.y, tid = threadIdx.x;
   const int g = blockIdx.x * CK_ESEG + tid / SPS, p = tid % SPS;
-  if (tid >= CK_ESEG * SPS || g >= a.G) return;
-  const ClockRow row = row_of(a, s);
-  const int64_t v0 = (int64_t)g * SEG + p;
+  if (tid >= CK_ESEG * SPS || g >= a.c.G) return;
   double e = 0.0;
-  if (v0 - p >= row.tail) {                     // the whole segment lies in the caller's row
-    const float* __restrict__ x = row.x + (v0 - row.tail);
-#pragma unroll 8
-    for (int j = 0; j < SEG_SYM; ++j) {
-      const float f = x[SPS * j];
-      const double d = __builtin_isfinite(f) ? (double)f : 0.0;
-      e += d * d;
-    }
-  } else {
-    for (int j = 0; j < SEG_SYM; ++j) {
-      const float f = row(v0 + SPS * j);
-      const double d = __builtin_isfinite(f) ? (double)f : 0.0;
-      e += d * d;
-    }
-  }
+  seg_samples(g, p, a.c.tail, [&e](float f) {
+    const double d = __builtin_isfinite(f) ? (double)f : 0.0;
+    e += d * d;
+  }, row_of(a, s));
   a.E[((int64_t)s * a.gstride + g) * SPS + p] = e;
-}
-
-// inclusive scan of one value per thread across the first nact threads of the workgroup (two LDS
-// slots, log2(nact) rounds); returns the slot that holds the result
-template <class T, class Op>
-__device__ __forceinline__ int block_scan(T (*buf)[CK_T], int tid, int nact, Op op) {
-  int cur = 0;
-  for (int off = 1; off < nact; off <<= 1) {
-    __syncthreads();
-    const T mine = buf[cur][tid];
-    buf[cur ^ 1][tid] = tid >= off ? op(buf[cur][tid - off], mine) : mine;
-    cur ^= 1;
-  }
-  __syncthreads();
-  return cur;
 }
 
 struct Sum4 {
@@ -135,24 +112,23 @@ struct Sum4 {
 __global__ __launch_bounds__(CK_T) void rds_clock_track_kernel(const ClockArgs a) {
   __shared__ uint8_t maps[2][CK_T][SPS];
   __shared__ Sum4 sums[2][CK_T];
-  const int s = blockIdx.x, tid = threadIdx.x, G = a.G;
+  const int s = blockIdx.x, tid = threadIdx.x, G = a.c.G;
   ClockState* st = a.state + s;
   const int phi_seed = st->phi;
   const int64_t sym_seed = st->symbols;
   int* __restrict__ info = a.info + (int64_t)s * a.gstride;
-  const double* __restrict__ E = a.E + (int64_t)s * a.gstride * SPS;
-  const double* __restrict__ ecar = a.ecar_in + (int64_t)s * CK_KEEP * SPS;
+  const EnergyWindow energy = energy_of(a, s);
 
   // phat of every segment: the window's vectors, oldest first
   for (int g = tid; g < G; g += CK_T) {
-    const int64_t gabs = a.seg0 + g;
+    const int64_t gabs = a.c.seg0 + g;
     const int w = gabs + 1 < a.window ? (int)(gabs + 1) : a.window;
     double A[SPS];
 #pragma unroll
     for (int p = 0; p < SPS; ++p) A[p] = 0.0;
     for (int k = w - 1; k >= 0; --k) {
       const int gl = g - k;                     // >= -CK_KEEP
-      const double* __restrict__ e = gl >= 0 ? E + (int64_t)gl * SPS : ecar + (CK_KEEP + gl) * SPS;
+      const double* __restrict__ e = energy.at(gl);
 #pragma unroll
       for (int p = 0; p < SPS; ++p) A[p] += e[p];
     }
@@ -169,22 +145,21 @@ __global__ __launch_bounds__(CK_T) void rds_clock_track_kernel(const ClockArgs a
   __syncthreads();
 
   // the map of this thread's chunk of segments
-  const int C = (G + CK_T - 1) / CK_T;
-  const int g_lo = tid * C < G ? tid * C : G, g_hi = g_lo + C < G ? g_lo + C : G;
+  const SegChunk ch = chunk_of(tid, G, CK_T);
+  const int g_lo = ch.lo, g_hi = ch.hi, nact = ch.nact;
   {
     int m[SPS];
 #pragma unroll
     for (int v = 0; v < SPS; ++v) m[v] = v;
     for (int g = g_lo; g < g_hi; ++g) {
       const int phat = info[g];
-      const bool first = a.seg0 + g == 0;
+      const bool first = a.c.seg0 + g == 0;
 #pragma unroll
       for (int v = 0; v < SPS; ++v) m[v] = first ? phat : step_phi(m[v], phat);
     }
 #pragma unroll
     for (int v = 0; v < SPS; ++v) maps[0][tid][v] = (uint8_t)m[v];
   }
-  const int nact = C > 0 ? (G + C - 1) / C : 0;                   // threads whose chunk is not empty
   int cur = 0;
   for (int off = 1; off < nact; off <<= 1) {    // inclusive scan: chunks 0 .. tid in order
     __syncthreads();
@@ -207,7 +182,7 @@ __global__ __launch_bounds__(CK_T) void rds_clock_track_kernel(const ClockArgs a
   int phi = phi_lo;
   for (int g = g_lo; g < g_hi; ++g) {
     const int phat = info[g];
-    const bool first = a.seg0 + g == 0;
+    const bool first = a.c.seg0 + g == 0;
     const int nphi = first ? phat : step_phi(phi, phat);
     int j0 = 0;
     if (!first && nphi != phi) {
@@ -258,12 +233,12 @@ __device__ __forceinline__ ClockPair pair_of(const ClockRow& row, int g, int k, 
 
 __global__ __launch_bounds__(CK_T) void rds_clock_counts_kernel(const ClockArgs a) {
   const int s = blockIdx.y, lane = threadIdx.x & 63, g = blockIdx.x * CK_NW + (threadIdx.x >> 6);
-  if (g >= a.G) return;                         // the whole wave
+  if (g >= a.c.G) return;                       // the whole wave
   const int* __restrict__ info = a.info + (int64_t)s * a.gstride;
   const int w = info[g];
   const int phi_before = g > 0 ? info[g - 1] & 0xff : a.call[s].phi_prev;
   const int cnt = SEG_SYM - (((w >> I_J0) & 3) - 1);
-  const bool act = lane < cnt && !(lane == 0 && a.seg0 + g == 0);
+  const bool act = lane < cnt && !(lane == 0 && a.c.seg0 + g == 0);
   bool change = false;
   if (act) {
     const ClockPair pr = pair_of(row_of(a, s), g, lane, w, phi_before);
@@ -290,22 +265,21 @@ struct Sum2 {
 __global__ __launch_bounds__(CK_T) void rds_clock_pair_kernel(const ClockArgs a) {
   __shared__ int maps[2][CK_T];
   __shared__ Sum2 sums[2][CK_T];
-  const int s = blockIdx.x, tid = threadIdx.x, G = a.G;
+  const int s = blockIdx.x, tid = threadIdx.x, G = a.c.G;
   ClockState* st = a.state + s;
   const int pi_seed = st->pi;
   const int64_t bits_seed = st->bits;
   int* __restrict__ info = a.info + (int64_t)s * a.gstride;
-  const int* __restrict__ cc = a.cc + (int64_t)s * a.gstride * 2;
-  const int* __restrict__ ccar = a.ccar_in + (int64_t)s * CK_KEEP * 2;
+  const CountWindow counts = counts_of(a, s);
 
   // every segment's map of pi from the windowed counts
   for (int g = tid; g < G; g += CK_T) {
-    const int64_t gabs = a.seg0 + g;
+    const int64_t gabs = a.c.seg0 + g;
     const int w = gabs + 1 < a.window ? (int)(gabs + 1) : a.window;
     int c0 = 0, c1 = 0;
     for (int k = w - 1; k >= 0; --k) {
       const int gl = g - k;
-      const int* __restrict__ c = gl >= 0 ? cc + (int64_t)gl * 2 : ccar + (CK_KEEP + gl) * 2;
+      const int* __restrict__ c = counts.at(gl);
       c0 += c[0];
       c1 += c[1];
     }
@@ -316,19 +290,18 @@ __global__ __launch_bounds__(CK_T) void rds_clock_pair_kernel(const ClockArgs a)
   }
   __syncthreads();
 
-  const int C = (G + CK_T - 1) / CK_T;
-  const int g_lo = tid * C < G ? tid * C : G, g_hi = g_lo + C < G ? g_lo + C : G;
+  const SegChunk ch = chunk_of(tid, G, CK_T);
+  const int g_lo = ch.lo, g_hi = ch.hi, nact = ch.nact;
   int cm = 2;                                   // the identity
   for (int g = g_lo; g < g_hi; ++g) cm = map2_compose(cm, (info[g] >> I_MAP) & 3);
   maps[0][tid] = cm;
-  const int nact = C > 0 ? (G + C - 1) / C : 0;                   // threads whose chunk is not empty
   const int mc = block_scan(maps, tid, nact, [](int p, int q) { return map2_compose(p, q); });
   int pi = tid == 0 ? pi_seed : map2_apply(maps[mc][tid - 1], pi_seed);
 
   Sum2 c = {0, 0};
   for (int g = g_lo; g < g_hi; ++g) {
     const int w = info[g];
-    const bool first = a.seg0 + g == 0;
+    const bool first = a.c.seg0 + g == 0;
     const int npi = map2_apply((w >> I_MAP) & 3, pi);
     const bool moved = !first && npi != pi;
     const bool excl = first || moved;
@@ -363,7 +336,7 @@ __global__ __launch_bounds__(CK_T) void rds_clock_pair_kernel(const ClockArgs a)
 
 __global__ __launch_bounds__(CK_T) void rds_clock_bits_kernel(const ClockArgs a) {
   const int s = blockIdx.y, lane = threadIdx.x & 63, g = blockIdx.x * CK_NW + (threadIdx.x >> 6);
-  if (g >= a.G) return;
+  if (g >= a.c.G) return;
   const int* __restrict__ info = a.info + (int64_t)s * a.gstride;
   const int w = info[g];
   const int cnt = SEG_SYM - (((w >> I_J0) & 3) - 1);
@@ -389,20 +362,12 @@ __global__ __launch_bounds__(CK_T) void rds_clock_finish_kernel(const ClockArgs 
     if (call.nbits > 0) b[0] = b[call.nbits];
   }
   // the next call's carried samples: the 24 before its first segment, and the tail
-  const int G = a.G;
-  const int64_t L = a.tail + a.n - (int64_t)G * SEG;             // < 768
+  const int G = a.c.G;
+  const int64_t L = a.c.tail + a.c.n - (int64_t)G * SEG;         // < 768
   if (i < SPS + L) a.carry_out[(int64_t)s * CK_CARRY + i] = row_of(a, s)((int64_t)G * SEG - SPS + i);
   // ... and the last CK_KEEP energy vectors and counts of (the carried ones, the call's)
-  if (i < CK_KEEP * SPS) {
-    const int gl = G - CK_KEEP + (int)i / SPS, p = (int)i % SPS;
-    a.ecar_out[(int64_t)s * CK_KEEP * SPS + i] = gl >= 0 ? a.E[((int64_t)s * a.gstride + gl) * SPS + p]
-                                                          : a.ecar_in[((int64_t)s * CK_KEEP + CK_KEEP + gl) * SPS + p];
-  }
-  if (i < CK_KEEP * 2) {
-    const int gl = G - CK_KEEP + (int)i / 2, p = (int)i % 2;
-    a.ccar_out[(int64_t)s * CK_KEEP * 2 + i] = gl >= 0 ? a.cc[((int64_t)s * a.gstride + gl) * 2 + p]
-                                                        : a.ccar_in[((int64_t)s * CK_KEEP + CK_KEEP + gl) * 2 + p];
-  }
+  if (i < CK_KEEP * SPS) a.ecar_out[(int64_t)s * CK_KEEP * SPS + i] = energy_of(a, s).roll(G, (int)i);
+  if (i < CK_KEEP * 2) a.ccar_out[(int64_t)s * CK_KEEP * 2 + i] = counts_of(a, s).roll(G, (int)i);
 }
 
 }  // namespace
@@ -411,9 +376,8 @@ struct sdr_rds_clock {
   sdr_ctx* ctx = nullptr;
   int S = 0, window = 4, hysteresis = 8;
   int64_t max_n = 0, gstride = 0, max_bits = 0, bit_stride = 0, diff_stride = 0;
-  // host-side: every stream of a call brings the same n
-  int64_t consumed = 0, seg0 = 0;
-  int tail = 0, cur = 0;
+  SegCursor seg;
+  DevMem mem;
   float* carry[2] = {nullptr, nullptr};
   double* ecar[2] = {nullptr, nullptr};
   int* ccar[2] = {nullptr, nullptr};
@@ -427,30 +391,6 @@ struct sdr_rds_clock {
   uint8_t* diff = nullptr;
   int* counts = nullptr;
 };
-
-namespace {
-
-size_t carry_bytes(const sdr_rds_clock* k) { return sizeof(float) * CK_CARRY * (size_t)k->S; }
-size_t ecar_bytes(const sdr_rds_clock* k) { return sizeof(double) * CK_KEEP * SPS * (size_t)k->S; }
-size_t ccar_bytes(const sdr_rds_clock* k) { return sizeof(int) * CK_KEEP * 2 * (size_t)k->S; }
-
-int clear_clock(sdr_rds_clock* k) {
-  hipStream_t st = k->ctx->stream;
-  for (int q = 0; q < 2; ++q) {
-    HIP_TRY(hipMemsetAsync(k->carry[q], 0, carry_bytes(k), st));
-    HIP_TRY(hipMemsetAsync(k->ecar[q], 0, ecar_bytes(k), st));
-    HIP_TRY(hipMemsetAsync(k->ccar[q], 0, ccar_bytes(k), st));
-  }
-  HIP_TRY(hipMemsetAsync(k->state, 0, sizeof(ClockState) * k->S, st));
-  HIP_TRY(hipMemsetAsync(k->call, 0, sizeof(ClockCall) * k->S, st));
-  HIP_TRY(hipMemsetAsync(k->counts, 0, sizeof(int) * k->S, st));
-  HIP_TRY(hipMemsetAsync(k->bits, 0, (size_t)k->bit_stride * k->S, st));
-  k->consumed = k->seg0 = 0;
-  k->tail = k->cur = 0;
-  return SDR_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -473,30 +413,25 @@ int sdr_rds_clock_create(sdr_ctx* c, int nstreams, int64_t max_n, sdr_rds_clock*
   k->bit_stride = ceil_div(k->max_bits + 2, 64) * 64;
   k->diff_stride = ceil_div(k->max_bits, 64) * 64;
   const size_t S = (size_t)nstreams, GS = S * (size_t)k->gstride;
-  hipError_t e = hipSuccess;
-  for (int q = 0; q < 2 && e == hipSuccess; ++q) {
-    e = hipMalloc(&k->carry[q], carry_bytes(k));
-    if (e == hipSuccess) e = hipMalloc(&k->ecar[q], ecar_bytes(k));
-    if (e == hipSuccess) e = hipMalloc(&k->ccar[q], ccar_bytes(k));
-  }
-  if (e == hipSuccess) e = hipMalloc(&k->state, sizeof(ClockState) * S);
-  if (e == hipSuccess) e = hipMalloc(&k->call, sizeof(ClockCall) * S);
-  if (e == hipSuccess) e = hipMalloc(&k->E, sizeof(double) * SPS * GS);
-  if (e == hipSuccess) e = hipMalloc(&k->info, sizeof(int) * GS);
-  if (e == hipSuccess) e = hipMalloc(&k->cc, sizeof(int) * 2 * GS);
-  if (e == hipSuccess) e = hipMalloc(&k->bit0, sizeof(int) * GS);
-  if (e == hipSuccess) e = hipMalloc(&k->bits, S * (size_t)k->bit_stride);
-  if (e == hipSuccess) e = hipMalloc(&k->diff, S * (size_t)k->diff_stride);
-  if (e == hipSuccess) e = hipMalloc(&k->counts, sizeof(int) * S);
-  if (e == hipSuccess) e = hipMemsetAsync(k->diff, 0, S * (size_t)k->diff_stride, c->stream);
-  if (e != hipSuccess) {
+  DevMem& m = k->mem;             // `true`: what a reset clears
+  m.get2(k->carry, CK_CARRY * S, true);
+  m.get2(k->ecar, CK_KEEP * SPS * S, true);
+  m.get2(k->ccar, CK_KEEP * 2 * S, true);
+  m.get(&k->state, S, true);
+  m.get(&k->call, S, true);
+  m.get(&k->E, SPS * GS);
+  m.get(&k->info, GS);
+  m.get(&k->cc, 2 * GS);
+  m.get(&k->bit0, GS);
+  m.get(&k->bits, S * (size_t)k->bit_stride, true);
+  m.get(&k->diff, S * (size_t)k->diff_stride);
+  m.get(&k->counts, S, true);
+  if (m.err == hipSuccess) m.err = hipMemsetAsync(k->diff, 0, S * (size_t)k->diff_stride, c->stream);
+  if (m.err == hipSuccess) m.err = m.zero(c->stream);
+  if (m.err != hipSuccess) {
+    const hipError_t e = m.err;
     sdr_rds_clock_destroy(k);
     return create_failed(e, "sdr_rds_clock_create");
-  }
-  const int rc = clear_clock(k);
-  if (rc != SDR_OK) {
-    sdr_rds_clock_destroy(k);
-    return rc;
   }
   *out = k;
   return SDR_OK;
@@ -505,27 +440,16 @@ int sdr_rds_clock_create(sdr_ctx* c, int nstreams, int64_t max_n, sdr_rds_clock*
 void sdr_rds_clock_destroy(sdr_rds_clock* k) {
   if (k == nullptr) return;
   if (k->ctx != nullptr && set_dev(k->ctx) == SDR_OK) (void)hipStreamSynchronize(k->ctx->stream);
-  for (int q = 0; q < 2; ++q) {
-    (void)hipFree(k->carry[q]);
-    (void)hipFree(k->ecar[q]);
-    (void)hipFree(k->ccar[q]);
-  }
-  (void)hipFree(k->state);
-  (void)hipFree(k->call);
-  (void)hipFree(k->E);
-  (void)hipFree(k->info);
-  (void)hipFree(k->cc);
-  (void)hipFree(k->bit0);
-  (void)hipFree(k->bits);
-  (void)hipFree(k->diff);
-  (void)hipFree(k->counts);
+  k->mem.release();
   delete k;
 }
 
 int sdr_rds_clock_reset(sdr_rds_clock* k) {
   if (k == nullptr) return fail(SDR_EINVAL, "sdr_rds_clock_reset: object is NULL");
   TRY(set_dev(k->ctx));
-  return clear_clock(k);
+  HIP_TRY(k->mem.zero(k->ctx->stream));
+  k->seg = SegCursor{};
+  return SDR_OK;
 }
 
 int sdr_rds_clock_set_params(sdr_rds_clock* k, int window, int hysteresis) {
@@ -540,34 +464,25 @@ int sdr_rds_clock_set_params(sdr_rds_clock* k, int window, int hysteresis) {
 }
 
 int sdr_rds_clock_process_dev(sdr_rds_clock* k, const float* rrc_i, int64_t n, int64_t stride) {
-  if (k == nullptr) return fail(SDR_EINVAL, "sdr_rds_clock_process_dev: object is NULL");
-  if (rrc_i == nullptr) return fail(SDR_EINVAL, "sdr_rds_clock_process_dev: rrc_i is NULL");
-  if (n < 0 || n > k->max_n)
-    return fail(SDR_EINVAL, "sdr_rds_clock_process_dev: n=%lld outside [0, max_n=%lld]", (long long)n, (long long)k->max_n);
-  if (stride < n) return fail(SDR_EINVAL, "sdr_rds_clock_process_dev: stride=%lld < n=%lld", (long long)stride, (long long)n);
-  if (((uintptr_t)rrc_i & 3) != 0) return fail(SDR_EINVAL, "sdr_rds_clock_process_dev: rrc_i must be aligned to 4 B");
+  TRY(seg_check_call(k, {rrc_i}, n, stride, "sdr_rds_clock_process_dev"));
   sdr_ctx* c = k->ctx;
   TRY(set_dev(c));
-  const int64_t G = (k->tail + n) / SEG;        // <= gstride: tail <= 767
   ClockArgs a;
   a.x = rrc_i;
-  a.n = n;
-  a.stride = stride;
-  a.seg0 = k->seg0;
-  a.G = (int)G;
-  a.tail = k->tail;
+  a.c = k->seg.begin(n, stride);
+  const int64_t G = a.c.G;                      // <= gstride: tail <= 767
   a.window = k->window;
   a.hysteresis = k->hysteresis;
   a.gstride = k->gstride;
   a.max_bits = k->max_bits;
   a.bit_stride = k->bit_stride;
   a.diff_stride = k->diff_stride;
-  a.carry_in = k->carry[k->cur];
-  a.carry_out = k->carry[k->cur ^ 1];
-  a.ecar_in = k->ecar[k->cur];
-  a.ecar_out = k->ecar[k->cur ^ 1];
-  a.ccar_in = k->ccar[k->cur];
-  a.ccar_out = k->ccar[k->cur ^ 1];
+  a.carry_in = k->carry[k->seg.cur];
+  a.carry_out = k->carry[k->seg.cur ^ 1];
+  a.ecar_in = k->ecar[k->seg.cur];
+  a.ecar_out = k->ecar[k->seg.cur ^ 1];
+  a.ccar_in = k->ccar[k->seg.cur];
+  a.ccar_out = k->ccar[k->seg.cur ^ 1];
   a.state = k->state;
   a.call = k->call;
   a.E = k->E;
@@ -587,10 +502,7 @@ int sdr_rds_clock_process_dev(sdr_rds_clock* k, const float* rrc_i, int64_t n, i
   hipLaunchKernelGGL(rds_clock_bits_kernel, dim3(gseg, S), dim3(CK_T), 0, c->stream, a);
   hipLaunchKernelGGL(rds_clock_finish_kernel, dim3((unsigned)ceil_div(fin, CK_T), S), dim3(CK_T), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
-  k->cur ^= 1;
-  k->tail = (int)(k->tail + n - G * SEG);
-  k->seg0 += G;
-  k->consumed += G * SEG;
+  k->seg.commit(a.c);
   return SDR_OK;
 }
 
@@ -618,15 +530,12 @@ int sdr_rds_clock_fetch(sdr_rds_clock* k, uint8_t* bits, int32_t* counts) {
 int sdr_rds_clock_state(sdr_rds_clock* k, int64_t* state) {
   if (k == nullptr) return fail(SDR_EINVAL, "sdr_rds_clock_state: object is NULL");
   if (state == nullptr) return fail(SDR_EINVAL, "sdr_rds_clock_state: state is NULL");
-  sdr_ctx* c = k->ctx;
-  TRY(set_dev(c));
-  std::vector<ClockState> st((size_t)k->S);
-  HIP_TRY(hipMemcpyAsync(st.data(), k->state, sizeof(ClockState) * st.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  std::vector<ClockState> st;
+  TRY(fetch_states(k->ctx, k->state, k->S, &st));
   for (int s = 0; s < k->S; ++s) {
     int64_t* o = state + (size_t)SDR_RDS_CLOCK_NSTATE * s;
-    o[0] = k->consumed;
-    o[1] = k->seg0;
+    o[0] = k->seg.seg0 * SEG;
+    o[1] = k->seg.seg0;
     o[2] = st[s].phi;
     o[3] = st[s].pi;
     o[4] = st[s].symbols;

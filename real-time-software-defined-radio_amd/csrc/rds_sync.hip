@@ -20,10 +20,13 @@
 //            lane to reach lose_after ends the round behind it.  SEARCH: a lane takes a position
 //            (512 a round), the predicate is balloted and the first set bit acquires.  The lanes
 //            store their records side by side; the wave writes the next state and carried bits.
+// The code -- H, the offset syndromes and types, the burst table, a window out of the LDS words,
+// its information word -- is rds_code.h's.
 #include <hip/hip_runtime.h>
 
 #include <new>
 
+#include "rds_code.h"
 #include "rds_links.h"
 #include "sdr_ctx.h"
 
@@ -33,37 +36,6 @@ namespace {
 
 constexpr int SY_T = 256, SY_TILE = 256, SY_NW = SY_T / 64, SY_CARRY = 51, SY_SEARCH = 8;
 static_assert(SY_TILE == SY_T, "one position of the row per thread");
-
-// parity matrix H as in rds.hip / capi.hip: row j belongs to the window's bit j, 10 bits with
-// column 0 the most significant; syndromes are written the same way
-constexpr uint16_t kHrow[26] = {0x200, 0x100, 0x080, 0x040, 0x020, 0x010, 0x008, 0x004, 0x002, 0x001, 0x2DC, 0x16E, 0x0B7,
-                                0x287, 0x39F, 0x313, 0x355, 0x376, 0x1BB, 0x201, 0x3DC, 0x1EE, 0x0F7, 0x2A7, 0x38F, 0x31B};
-// offset syndromes by type: A, B, C, D, C'
-constexpr uint32_t SYN_A = 0x3D8, SYN_B = 0x3D4, SYN_C = 0x25C, SYN_D = 0x258, SYN_CP = 0x3CC;
-constexpr int TYPE_NONE = 7, TYPE_CP = 4;
-
-// column c of H as a mask over the window word (bit j = the window's bit j)
-constexpr uint32_t col_mask(int c) {
-  uint32_t m = 0;
-  for (int j = 0; j < 26; ++j) m |= (uint32_t)((kHrow[j] >> (9 - c)) & 1) << j;
-  return m;
-}
-template <int C>
-__device__ __forceinline__ uint32_t parity_col(uint32_t v) {
-  constexpr uint32_t m = col_mask(C);
-  return (uint32_t)(__popc(v & m) & 1) << (9 - C);
-}
-__device__ __forceinline__ uint32_t syndrome_of(uint32_t v) {
-  return parity_col<0>(v) | parity_col<1>(v) | parity_col<2>(v) | parity_col<3>(v) | parity_col<4>(v) | parity_col<5>(v) |
-         parity_col<6>(v) | parity_col<7>(v) | parity_col<8>(v) | parity_col<9>(v);
-}
-__device__ __forceinline__ int type_of(uint32_t s) {
-  return s == SYN_A ? 0 : s == SYN_B ? 1 : s == SYN_C ? 2 : s == SYN_D ? 3 : s == SYN_CP ? TYPE_CP : TYPE_NONE;
-}
-__device__ __forceinline__ uint32_t syn_of_type(int t) {
-  return t == 0 ? SYN_A : t == 1 ? SYN_B : t == 2 ? SYN_C : t == 3 ? SYN_D : SYN_CP;
-}
-__device__ __forceinline__ int slot_of_type(int t) { return t == TYPE_CP ? 2 : t; }
 
 // a window's entry: the syndrome, the offset type (TYPE_NONE: none), the acquisition predicate
 // and the 16 information bits
@@ -144,18 +116,11 @@ __global__ __launch_bounds__(SY_T) void rds_sync_windows_kernel(const SyncArgs a
   }
   __syncthreads();
   if (i >= r.W) return;
-  auto window = [&](int o) -> uint32_t {        // the 26 bits from bit o of dw on, the first one bit 0
-    const int q = o >> 5, sh = o & 31;
-    const unsigned long long pair = ((unsigned long long)dw[q + 1] << 32) | dw[q];
-    return (uint32_t)(pair >> sh) & 0x3ffffffu;
-  };
-  const uint32_t v = window(32 + tid), vp = window(6 + tid);
+  const uint32_t v = window_at(dw, 32 + tid), vp = window_at(dw, 6 + tid);      // the thread's, and the one 26 bits before it
   const uint32_t syn = syndrome_of(v);
   const int typ = type_of(syn), typ_p = type_of(syndrome_of(vp));
   const bool acq = i >= 26 && typ != TYPE_NONE && typ_p != TYPE_NONE && slot_of_type(typ) == ((slot_of_type(typ_p) + 1) & 3);
-  // information word: the window's first 16 bits, the first one most significant
-  const uint32_t word = __brev(v) >> 16;
-  a.win[(int64_t)s * a.win_stride + i] = (word << E_WORD) | ((uint32_t)acq << E_ACQ) | ((uint32_t)typ << E_TYPE) | syn;
+  a.win[(int64_t)s * a.win_stride + i] = (info_word(v) << E_WORD) | ((uint32_t)acq << E_ACQ) | ((uint32_t)typ << E_TYPE) | syn;
 }
 
 // a block of the given type: status 0 / 1 / 2 and the information word after correction
@@ -313,14 +278,6 @@ __global__ __launch_bounds__(64) void rds_sync_track_kernel(const SyncArgs a) {
   }
 }
 
-// the syndrome of an error pattern given with the block's first bit as bit 25
-uint32_t host_syndrome(uint32_t pat) {
-  uint32_t s = 0;
-  for (int j = 0; j < 26; ++j)
-    if ((pat >> (25 - j)) & 1u) s ^= kHrow[j];
-  return s;
-}
-
 }  // namespace
 
 struct sdr_rds_sync {
@@ -333,34 +290,14 @@ struct sdr_rds_sync {
   int64_t* rec = nullptr;
   int64_t* nrec = nullptr;
   uint32_t host_table[1024] = {};
+  DevMem mem;
 };
 
 namespace {
 
-int clear_sync(sdr_rds_sync* y) {
-  hipStream_t st = y->ctx->stream;
-  HIP_TRY(hipMemsetAsync(y->state, 0, sizeof(SyncState) * y->S, st));
-  HIP_TRY(hipMemsetAsync(y->nrec, 0, sizeof(int64_t) * y->S, st));
-  return SDR_OK;
-}
-
-// Every error pattern inside the block whose first and last flipped bits are at most
-// max_burst - 1 apart (26 / 51 / 99 / 191 / 367 patterns for 1 .. 5): their syndromes are
-// distinct and non-zero, so the table by syndrome is the whole decoder.
+// the decoder's table (rds_code.h burst_table) to the device
 int build_table(sdr_rds_sync* y, int max_burst) {
-  for (uint32_t& t : y->host_table) t = 0u;
-  for (int len = 1; len <= max_burst; ++len) {
-    const int inner = len > 2 ? len - 2 : 0;
-    for (int first = 0; first + len <= 26; ++first)
-      for (uint32_t mid = 0; mid < (1u << inner); ++mid) {
-        uint32_t pat = 1u << (25 - first);
-        if (len > 1) pat |= 1u << (25 - first - (len - 1));
-        for (int k = 0; k < inner; ++k) pat |= ((mid >> k) & 1u) << (25 - first - 1 - k);
-        const uint32_t s = host_syndrome(pat);
-        if (s == 0u || y->host_table[s] != 0u) return fail(SDR_EINVAL, "sdr_rds_sync_set_params: burst syndromes collide");
-        y->host_table[s] = (1u << 16) | (pat >> 10);
-      }
-  }
+  if (burst_table(max_burst, y->host_table)) return fail(SDR_EINVAL, "sdr_rds_sync_set_params: burst syndromes collide");
   HIP_TRY(hipMemcpyAsync(y->table, y->host_table, sizeof(y->host_table), hipMemcpyHostToDevice, y->ctx->stream));
   HIP_TRY(hipStreamSynchronize(y->ctx->stream));
   return SDR_OK;
@@ -411,17 +348,19 @@ int sdr_rds_sync_create(sdr_ctx* c, int nstreams, int64_t max_bits, sdr_rds_sync
   y->max_records = max_bits / 26 + 3;
   y->win_stride = ceil_div(max_bits + SY_CARRY, SY_TILE) * SY_TILE;
   const size_t S = (size_t)nstreams;
-  hipError_t e = hipMalloc(&y->state, sizeof(SyncState) * S);
-  if (e == hipSuccess) e = hipMalloc(&y->win, sizeof(uint32_t) * S * y->win_stride);
-  if (e == hipSuccess) e = hipMalloc(&y->table, sizeof(y->host_table));
-  if (e == hipSuccess) e = hipMalloc(&y->rec, sizeof(int64_t) * 4 * S * (size_t)y->max_records);
-  if (e == hipSuccess) e = hipMalloc(&y->nrec, sizeof(int64_t) * S);
-  if (e != hipSuccess) {
+  DevMem& m = y->mem;             // `true`: what a reset clears
+  m.get(&y->state, S, true);
+  m.get(&y->win, S * y->win_stride);
+  m.get(&y->table, 1024);
+  m.get(&y->rec, 4 * S * (size_t)y->max_records);
+  m.get(&y->nrec, S, true);
+  if (m.err == hipSuccess) m.err = m.zero(c->stream);
+  if (m.err != hipSuccess) {
+    const hipError_t e = m.err;
     sdr_rds_sync_destroy(y);
     return create_failed(e, "sdr_rds_sync_create");
   }
-  int rc = clear_sync(y);
-  if (rc == SDR_OK) rc = build_table(y, y->max_burst);
+  const int rc = build_table(y, y->max_burst);
   if (rc != SDR_OK) {
     sdr_rds_sync_destroy(y);
     return rc;
@@ -433,18 +372,15 @@ int sdr_rds_sync_create(sdr_ctx* c, int nstreams, int64_t max_bits, sdr_rds_sync
 void sdr_rds_sync_destroy(sdr_rds_sync* y) {
   if (y == nullptr) return;
   if (y->ctx != nullptr && set_dev(y->ctx) == SDR_OK) (void)hipStreamSynchronize(y->ctx->stream);
-  (void)hipFree(y->state);
-  (void)hipFree(y->win);
-  (void)hipFree(y->table);
-  (void)hipFree(y->rec);
-  (void)hipFree(y->nrec);
+  y->mem.release();
   delete y;
 }
 
 int sdr_rds_sync_reset(sdr_rds_sync* y) {
   if (y == nullptr) return fail(SDR_EINVAL, "sdr_rds_sync_reset: object is NULL");
   TRY(set_dev(y->ctx));
-  return clear_sync(y);
+  HIP_TRY(y->mem.zero(y->ctx->stream));
+  return SDR_OK;
 }
 
 int sdr_rds_sync_set_params(sdr_rds_sync* y, int max_burst, int lose_after) {
@@ -497,11 +433,8 @@ int sdr_rds_sync_blocks(sdr_rds_sync* y, int64_t* rec, int64_t* n_rec) {
 
 int sdr_rds_sync_state(sdr_rds_sync* y, int32_t* synced, int64_t* next_pos, int64_t* counters) {
   if (y == nullptr) return fail(SDR_EINVAL, "sdr_rds_sync_state: object is NULL");
-  sdr_ctx* c = y->ctx;
-  TRY(set_dev(c));
-  std::vector<SyncState> st((size_t)y->S);
-  HIP_TRY(hipMemcpyAsync(st.data(), y->state, sizeof(SyncState) * st.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  std::vector<SyncState> st;
+  TRY(fetch_states(y->ctx, y->state, y->S, &st));
   for (int s = 0; s < y->S; ++s) {
     if (synced) synced[s] = st[s].mode == MODE_SYNC;
     if (next_pos) next_pos[s] = st[s].pos;

@@ -157,6 +157,52 @@ inline int create_failed(hipError_t e, const char* what) {
   return fail(e == hipErrorOutOfMemory ? SDR_ENOMEM : SDR_EHIP, "%s: %s", what, hipGetErrorString(e));
 }
 
+// The device arrays an object owns.  A create calls get() for each and looks at `err` once: the
+// first failure stays there and the gets after it do nothing.  zero() clears the arrays that a
+// reset clears; release() frees them all, after a partial failure as well.
+struct DevMem {
+  struct Item {
+    void* p;
+    size_t bytes;
+    bool zeroed;
+  };
+  std::vector<Item> items;
+  hipError_t err = hipSuccess;
+
+  template <class T>
+  void get(T** p, size_t count, bool zeroed_on_reset = false) {
+    if (err != hipSuccess) return;
+    err = hipMalloc(p, count * sizeof(T));
+    if (err == hipSuccess) items.push_back(Item{*p, count * sizeof(T), zeroed_on_reset});
+  }
+  // an array in each of two slots: a call reads slot[cur] and fills the other (rds_seg.h SegCursor)
+  template <class T>
+  void get2(T* (&slot)[2], size_t count, bool zeroed_on_reset = false) {
+    get(&slot[0], count, zeroed_on_reset);
+    get(&slot[1], count, zeroed_on_reset);
+  }
+  hipError_t zero(hipStream_t st) const {
+    hipError_t e = hipSuccess;
+    for (const Item& it : items)
+      if (it.zeroed && e == hipSuccess) e = hipMemsetAsync(it.p, 0, it.bytes, st);
+    return e;
+  }
+  void release() {
+    for (const Item& it : items) (void)hipFree(it.p);
+    items.clear();
+  }
+};
+
+// an object's per-stream struct array on the host, after waiting for the calls in flight
+template <class T>
+int fetch_states(sdr_ctx* c, const T* dev, int nstreams, std::vector<T>* out) {
+  TRY(set_dev(c));
+  out->resize((size_t)nstreams);
+  HIP_TRY(hipMemcpyAsync(out->data(), dev, sizeof(T) * out->size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return SDR_OK;
+}
+
 // rows of row_bytes bytes each; on the host `pitch` bytes apart, packed on the device
 struct HostRows {
   size_t rows, row_bytes, pitch;

@@ -1,6 +1,7 @@
-"""What the row blocks' timing tools share (ddc_time, pfb_time, rsmp_time, spectrum_time,
-rds_link_time): the HIP-event loop, the parser of a build's kernel resource remarks and the copy
-bandwidth of the box."""
+"""What the blocks' timing tools share (ddc_time, pfb_time, rsmp_time, spectrum_time, rspec_time,
+iqc_time, blend_time, rds_link_time, rds_sync_time, rds_clock_time, rds_carrier_time): the
+HIP-event loop, best and median of its repeats, the parser of a build's kernel resource remarks
+and the copy bandwidth of the box."""
 import ctypes
 import os
 import re
@@ -44,6 +45,12 @@ def event_ms(ctx, calls, reps, warmup, before=None):
             ms[i].append(tm.elapsed_ms(e0, e1))
     tm.close()
     return [np.array(v) for v in ms]
+
+
+def stats(ms):
+    """Best and median of the repeats, in microseconds."""
+    ms = np.asarray(ms)
+    return {"best_us": round(float(ms.min()) * 1e3, 1), "median_us": round(float(np.median(ms)) * 1e3, 1)}
 
 
 def kernel_resources(path, pattern, label, fields):

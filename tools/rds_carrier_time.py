@@ -23,16 +23,11 @@ import os
 import numpy as np
 
 import _blocktime as bt
-from _blocktime import rtsdr
+from _blocktime import rtsdr, stats
 from rds_link_time import make_rows
 
 SHAPES = ((8, 256 * 3648), (96, 3648))
 SIGMA = 0.3
-
-
-def stats(ms):
-    ms = np.asarray(ms)
-    return {"best_us": round(float(ms.min()) * 1e3, 1), "median_us": round(float(np.median(ms)) * 1e3, 1)}
 
 
 def make_pairs(S, n):

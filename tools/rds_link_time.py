@@ -44,7 +44,7 @@ def make_rows(S, n, sigma):
 
 def event_times(ctx, call, reps, warmup, before=None):
     (ms,) = bt.event_ms(ctx, [call], reps, warmup, before)
-    return {"best_us": round(float(ms.min()) * 1e3, 1), "median_us": round(float(np.median(ms)) * 1e3, 1)}
+    return bt.stats(ms)
 
 
 def wall_best(fn, reps):
