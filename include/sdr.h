@@ -46,6 +46,7 @@ enum {
 };
 
 enum { SDR_IQ_F32 = 0, SDR_IQ_U8 = 1 };                  /* interleaved IQ sample types */
+enum { SDR_IQ_S8 = 2, SDR_IQ_S16 = 3 };                  /* raw capture types: accepted by sdr_ingest_create only */
 enum { SDR_PRE_NONE = 0, SDR_PRE_SQUARE = 1, SDR_PRE_MIX = 2 }; /* FIR input pre-ops */
 enum { SDR_REAL_F32 = 0, SDR_REAL_F64 = 1 };              /* real sample types (PSD) */
 #define SDR_DFT_MAX_N (1 << 16)
@@ -442,6 +443,59 @@ int sdr_rx_stage_ms(sdr_rx* rx, float* ms);
 int sdr_rx_state(sdr_rx* rx, double* phase, double* pll_stereo, double* pll_rds);
 /* sdr_pll_stats of the receiver's context, after waiting for every block in flight */
 int sdr_rx_pll_stats(sdr_rx* rx, int64_t* out, int reset);
+
+/* ---- capture ingest: raw sc8 / sc16 / u8 / f32 bytes to the f32 capture, with a level meter ----
+ * The stage in front of sdr_iqc: the raw bytes of a capture block in device memory in, the block as
+ * interleaved f32 out -- the buffer sdr_iqc / sdr_spec / sdr_ddc / sdr_pfb read -- and the level
+ * meter a user sets the front end's gain by, taken where the ADC's codes are still seen.  The
+ * reference has no such stage; the definition is rtsdr.ingest_model (capture.py):
+ *   code c of a value x: SDR_IQ_U8 x - 128, SDR_IQ_S8 x (bits = 8 both); SDR_IQ_S16 x, a native
+ *   little-endian int16 that holds a right-justified, sign-extended ADC code of `bits` bits, 2..16
+ *   (16 unless params say otherwise; a 12-bit ADC: 12).  out = f32(c 2^-(bits - 1)), exact for
+ *   every code; for u8 the project's (x - 128) / 128.  SDR_IQ_F32 passes through bit for bit, NaN
+ *   and infinities included.  swap != 0 exchanges I and Q in out (a front end with an inverted
+ *   spectrum); the meter is taken on the input and does not depend on it.
+ *   meter of a call, integer types, all exact: n; clipped, the samples whose I or Q code is
+ *   >= 2^(bits - 1) - 1 or <= -2^(bits - 1) (codes beyond a narrower `bits` count too); peak_code =
+ *   max |c| over I and Q; sumsq_code = sum (cI^2 + cQ^2) (below 2^62); peak = peak_code 2^-(bits - 1)
+ *   and sumsq = f64(sumsq_code) 2^-2(bits - 1); nonfinite = 0.
+ *   meter of a call, f32: nonfinite, the samples with a non-finite I or Q, left out of everything
+ *   else; clipped, |I| >= 1 or |Q| >= 1; peak, the largest |x|; sumsq, the f64 sum of the f64 squares
+ *   in the kernels' fixed order; peak_code = sumsq_code = 0.
+ *   carried from call to call: calls, total_n, total_clipped.  sdr_ingest_reset zeroes the meter.
+ * Two launches per call (csrc/ingest.hip: the conversion with one partial record per workgroup,
+ * then one wave that folds them), no host synchronisation, no atomics: the same call gives the same
+ * bits.  With meter == 0 the stage is the conversion launch alone and the meter stays as reset left
+ * it.  The block is cut into at most 2 048 chunks, none but the last shorter than
+ * SDR_INGEST_CHUNK samples, one workgroup each.  sdr_ingest_process_dev: async; raw aligned to one
+ * complex sample (2 B u8 / s8, 4 B s16, 8 B f32), out to 8 B; 1 <= n <= 2^31 - 1; all sample offsets
+ * are 64-bit.  For f32, out == raw (in place) is allowed; any other overlap of the two extents is
+ * refused.  sdr_ingest_meter_get synchronises; sdr_ingest_meter_dev: the device copy, for a
+ * consumer on the stream.  Every other entry point that takes an iq_dtype refuses SDR_IQ_S8 and
+ * SDR_IQ_S16.
+ * SDR_EINVAL (before any device work): NULL pointers, bad dtype, bits outside 2..16 (s16) or not
+ * the container's width (the other types; 0 stands for the container's width everywhere), n outside
+ * [1, 2^31 - 1], a misaligned pointer, an overlap.  No host fallback. */
+#define SDR_INGEST_CHUNK 4096
+typedef struct sdr_ingest_params {
+  int bits;    /* width of the ADC code in its container; 0: the container's width */
+  int swap;    /* exchange I and Q in out */
+  int meter;   /* take the level meter */
+} sdr_ingest_params;  /* NULL: container width, 0, 1 */
+typedef struct sdr_ingest_meter {
+  int64_t n, clipped, nonfinite, peak_code;
+  uint64_t sumsq_code;
+  double peak, sumsq;
+  int64_t calls, total_n, total_clipped;
+} sdr_ingest_meter;
+typedef struct sdr_ingest sdr_ingest;
+int  sdr_ingest_create(sdr_ctx* ctx, int iq_dtype /* SDR_IQ_F32 | _U8 | _S8 | _S16 */, const sdr_ingest_params* params, sdr_ingest** out);
+void sdr_ingest_destroy(sdr_ingest* ing);
+int  sdr_ingest_reset(sdr_ingest* ing);                                                   /* async */
+int  sdr_ingest_process_dev(sdr_ingest* ing, const void* raw, int64_t n, float* out);     /* async */
+int  sdr_ingest_run(sdr_ingest* ing, const void* raw_host, int64_t n, float* out_host);   /* sync */
+int  sdr_ingest_meter_get(sdr_ingest* ing, sdr_ingest_meter* host);                       /* synchronises */
+int  sdr_ingest_meter_dev(sdr_ingest* ing, const sdr_ingest_meter** dev);
 
 /* ---- IQ imbalance and DC offset correction of the capture -----------------------------------
  * The stage in front of sdr_spec / sdr_ddc / sdr_pfb: one block of a capture in device memory

@@ -29,20 +29,24 @@ stream's demodulated row and the stereo / RDS indicators behind the receiver: Ro
 Receiver.mpx_spectrum), mpx_quality (host); the stereo blend and noise mute that act on that quality
 on the device: BlendControl, BlendParams, audio_blend_dev, Receiver(blend=True); and in front of all of
 the capture's stages, the correction of a direct-conversion front end's DC offset and IQ imbalance:
-IqBalance (host, numpy f64: the specification) and IqCorrector (device).
+IqBalance (host, numpy f64: the specification) and IqCorrector (device); and in front of that, the
+raw formats wideband front ends write (signed 8- and 16-bit IQ, narrower ADC codes in 16-bit words)
+as the float32 capture, with a level meter of the ADC's codes: ingest_model, capture_format (host,
+numpy: the specification) and CaptureIngest (device).
 See DESIGN.md and INTEGRATION.md.
 """
 from . import design, synth  # noqa: F401
-from ._lib import (SDR_IQ_F32, SDR_IQ_U8, SDR_PRE_MIX, SDR_PRE_NONE, SDR_PRE_SQUARE, Context,  # noqa: F401
+from ._lib import (SDR_IQ_F32, SDR_IQ_S8, SDR_IQ_S16, SDR_IQ_U8, SDR_PRE_MIX, SDR_PRE_NONE, SDR_PRE_SQUARE, Context,  # noqa: F401
                    DeviceBuffer, SdrError, SdrUnavailable, Timer, device_count, device_info, get_context,
                    load_library)
-from .blocks import (BlendControl, BlendParams, BlendState, Channelizer, FilterBank, IqCorrector, MonoBlockProcessor, MpxQuality, RdsBlockProcessor, RdsCarrierBank, RdsClockBank, RdsLinkBank, RdsLinkLayer, RdsSyncBank,  # noqa: F401
+from .blocks import (BlendControl, BlendParams, BlendState, CaptureIngest, Channelizer, FilterBank, IqCorrector, MonoBlockProcessor, MpxQuality, RdsBlockProcessor, RdsCarrierBank, RdsClockBank, RdsLinkBank, RdsLinkLayer, RdsSyncBank,  # noqa: F401
                      Receiver, RowResampler, RowSpectrum, Spectrum, StereoBlockProcessor, find_channels, mpx_quality, rds_groups,
                      spectrum_rows)
 from .rdssync import RdsBlockSync, RdsProgramme  # noqa: F401
 from .rdsclock import RdsSymbolClock  # noqa: F401
 from .rdscarrier import RdsCarrierPhase  # noqa: F401
 from .iqbalance import IqBalance, IqState  # noqa: F401
+from .capture import IngestMeter, capture_format, ingest_model  # noqa: F401
 from .design import impulseResponseRootRaisedCosine, my_filterImpulseResponse  # noqa: F401
 from .dsp import (DFT, MonoState, estimatePSD, fm_mono_range, fm_mono_streams, split_halo, fmDemodArctan, fmPll, lfilter, lfilter_decim,  # noqa: F401
                   audio_blend_dev, audio_out, deemphasis, iir1, mono_block, my_convoloution, resample, rf_frontend_block)

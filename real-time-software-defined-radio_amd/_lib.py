@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("SDR_LIB", os.path.join(_HERE, "libsdr.so"))
 SDR_OK, SDR_EINVAL, SDR_EHIP, SDR_ENOMEM, SDR_EUNSUPPORTED, SDR_EDOMAIN = 0, -1, -2, -3, -4, -5
 SDR_REAL_F32, SDR_REAL_F64 = 0, 1
 SDR_IQ_F32, SDR_IQ_U8 = 0, 1
+SDR_IQ_S8, SDR_IQ_S16 = 2, 3                      # raw capture types: sdr_ingest_create only
 SDR_PRE_NONE, SDR_PRE_SQUARE, SDR_PRE_MIX = 0, 1, 2
 # multi-stream receiver (include/sdr.h sdr_rx_*)
 SDR_RX_AUDIO, SDR_RX_STEREO, SDR_RX_RDS = 1, 2, 4
@@ -35,6 +36,7 @@ SDR_RDS_LINKS_MIN_N, SDR_RDS_LINKS_FAULT, SDR_RDS_LINKS_OVERFLOW = 1536, 1, 2
 SDR_RDS_CLOCK_NSTATE = 10
 SDR_RDS_CARRIER_NSTATE = 7
 SDR_IQC_NSTATE, SDR_IQC_CHUNK = 12, 4096   # the corrector of the capture (include/sdr.h sdr_iqc_*)
+SDR_INGEST_CHUNK = 4096                           # capture ingest (include/sdr.h sdr_ingest_*)
 PLL_STATS = ("recurrences", "spec_r0", "spec_r1", "spec_r2", "sequential", "long_guessed", "long_chained",
              "long_maxgap", "long_stops", "long_tail", "long_linear")
 
@@ -131,6 +133,13 @@ SIGNATURES = {
     "sdr_rx_pll_stats": (_i32, [_vp, _vp, _i32]),
     "sdr_rx_set_timing": (_i32, [_vp, _i32]),
     "sdr_rx_stage_ms": (_i32, [_vp, _fp]),
+    "sdr_ingest_create": (_i32, [_vp, _i32, _vp, _c.POINTER(_vp)]),
+    "sdr_ingest_destroy": (None, [_vp]),
+    "sdr_ingest_reset": (_i32, [_vp]),
+    "sdr_ingest_process_dev": (_i32, [_vp, _vp, _i64, _vp]),
+    "sdr_ingest_run": (_i32, [_vp, _vp, _i64, _vp]),
+    "sdr_ingest_meter_get": (_i32, [_vp, _vp]),
+    "sdr_ingest_meter_dev": (_i32, [_vp, _c.POINTER(_vp)]),
     "sdr_iqc_create": (_i32, [_vp, _i32, _vp, _c.POINTER(_vp)]),
     "sdr_iqc_destroy": (None, [_vp]),
     "sdr_iqc_reset": (_i32, [_vp]),

@@ -23,6 +23,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from . import capture
 from . import design
 from . import iqbalance
 from ._lib import RX_FILTERS, RX_OUTPUTS, SDR_IQ_F32, SDR_IQ_U8, SDR_RX_AUDIO, SDR_RX_RDS, SDR_RX_STEREO, check, f64p
@@ -863,6 +864,100 @@ def rds_groups(events):
         if t == 0 and all((p + 26 * k, k) in ok for k in (1, 2, 3)):
             groups.append(tuple(ok[(p + 26 * k, k)] for k in range(4)))
     return groups
+
+
+class _IngestParamsC(ctypes.Structure):                          # include/sdr.h sdr_ingest_params
+    _fields_ = [("bits", ctypes.c_int), ("swap", ctypes.c_int), ("meter", ctypes.c_int)]
+
+
+class _IngestMeterC(ctypes.Structure):                           # include/sdr.h sdr_ingest_meter
+    _fields_ = ([(k, ctypes.c_int64) for k in ("n", "clipped", "nonfinite", "peak_code")] + [("sumsq_code", ctypes.c_uint64)] +
+                [(k, ctypes.c_double) for k in ("peak", "sumsq")] + [(k, ctypes.c_int64) for k in ("calls", "total_n", "total_clipped")])
+
+
+class CaptureIngest(_Handle):
+    """The raw bytes of a capture block to the float32 capture on the GPU, with a level meter
+    (sdr_ingest, csrc/ingest.hip): the stage in front of IqCorrector.  `fmt` is 'cu8', 'cs8', 'cs16'
+    or 'cf32' (or numpy's uint8, int8, int16, float32; capture_format maps file and SigMF names);
+    `bits` is the width of the ADC's code in a cs16 word (12 for a 12-bit ADC); swap exchanges I and
+    Q.  process_dev reads the bytes in device memory -- a quarter (cs8) or half (cs16) of what the
+    float32 block would have cost to upload -- and writes interleaved float32, out = code 2^-(bits - 1),
+    the buffer every stage behind it reads.  With meter=True a second, one-wave launch leaves the
+    call's meter in device memory: the samples on a rail, the peak and the sum of squares of the
+    ADC's codes, exact, and the totals over calls; meter() fetches it (IngestMeter: power_dbfs,
+    peak_dbfs, clip_share).  With meter=False the stage is the conversion alone and the meter stays
+    zero.  Nothing returns to the host unless meter() is asked.
+
+    The rule is rtsdr.ingest_model's (capture.py), bit for bit.  For cf32 the block passes through
+    unchanged (swap aside) and out_ptr == raw_ptr is allowed.  The arguments are checked before a
+    context exists; the device object is made at the first call that needs it."""
+
+    CHUNK = _lib.SDR_INGEST_CHUNK                                # samples of a workgroup's chunk (at least)
+    MAX_N = capture.MAX_N
+    _prefix = "sdr_ingest"
+    _DTYPES = {"cf32": _lib.SDR_IQ_F32, "cu8": _lib.SDR_IQ_U8, "cs8": _lib.SDR_IQ_S8, "cs16": _lib.SDR_IQ_S16}
+
+    def __init__(self, fmt, bits=None, swap: bool = False, meter: bool = True, ctx=None):
+        self.fmt, self.bits = capture.check_format(fmt, bits)
+        self.swap, self.metered = bool(swap), bool(meter)
+        self.es = 2 * capture.FORMATS[self.fmt][0].itemsize      # bytes of a complex sample
+        self._ctx = ctx
+
+    def _open(self):
+        if self.handle is None:
+            self.ctx = self._ctx if self._ctx is not None else _lib.get_context()
+            self.lib = self.ctx.lib
+            h = ctypes.c_void_p()
+            prm = _IngestParamsC(self.bits, int(self.swap), int(self.metered))
+            check(self.lib.sdr_ingest_create(self.ctx.handle, self._DTYPES[self.fmt], ctypes.byref(prm), ctypes.byref(h)), "sdr_ingest_create")
+            self.handle = h
+        return self.handle
+
+    def process_dev(self, raw_ptr: int, n: int, out_ptr: int):
+        """n complex samples of the format at device pointer raw_ptr -> n complex float32 at out_ptr;
+        async on the context stream."""
+        n, raw_ptr, out_ptr = int(n), int(raw_ptr or 0), int(out_ptr or 0)
+        if not raw_ptr or not out_ptr:
+            raise ValueError("raw_ptr or out_ptr is NULL")
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError(f"n={n} outside [1, 2^31 - 1]")
+        if raw_ptr % self.es or out_ptr % 8:
+            raise ValueError(f"raw_ptr must be aligned to one complex sample ({self.es} B) and out_ptr to 8 B")
+        if raw_ptr < out_ptr + 8 * n and out_ptr < raw_ptr + self.es * n and not (self.fmt == "cf32" and raw_ptr == out_ptr):
+            raise ValueError("raw and out overlap (only out_ptr == raw_ptr of a cf32 ingest may)")
+        h = self._open()
+        check(self.lib.sdr_ingest_process_dev(h, raw_ptr, n, out_ptr), "sdr_ingest_process_dev")
+
+    def run(self, raw) -> np.ndarray:
+        """A capture block from the host (values of the format's type, raw bytes, or complex64 for
+        cf32) -> interleaved float32 (2 n values); synchronous (sdr_ingest_run)."""
+        raw = capture.as_raw(raw, self.fmt)
+        n = raw.size // 2
+        out = np.empty(2 * n, dtype=np.float32)
+        h = self._open()
+        check(self.lib.sdr_ingest_run(h, raw.ctypes.data, n, out.ctypes.data), "sdr_ingest_run")
+        return out
+
+    def meter(self) -> "capture.IngestMeter":
+        """The meter of the last call and the totals since the last reset (sdr_ingest_meter_get;
+        synchronises)."""
+        m = _IngestMeterC()
+        h = self._open()
+        check(self.lib.sdr_ingest_meter_get(h, ctypes.byref(m)), "sdr_ingest_meter_get")
+        return capture.IngestMeter(*(getattr(m, k) for k in capture.IngestMeter._fields))
+
+    @property
+    def meter_ptr(self) -> int:
+        """The device copy of the meter, a struct sdr_ingest_meter (sdr_ingest_meter_dev)."""
+        p = ctypes.c_void_p()
+        h = self._open()
+        check(self.lib.sdr_ingest_meter_dev(h, ctypes.byref(p)), "sdr_ingest_meter_dev")
+        return p.value
+
+    def reset(self):
+        """Zero the meter and its totals (async)."""
+        h = self._open()
+        check(self.lib.sdr_ingest_reset(h), "sdr_ingest_reset")
 
 
 class _IqcParamsC(ctypes.Structure):                             # include/sdr.h sdr_iqc_params

@@ -32,6 +32,7 @@
 #include <new>
 #include <type_traits>
 
+#include "sdr_chunk.h"
 #include "sdr_ctx.h"
 
 #pragma clang fp contract(off)
@@ -50,18 +51,7 @@ static_assert((uint64_t)IQC_U8_FLUSH * IQC_U * 8 * 255 * 255 <= 0xffffffffull, "
 static_assert(SDR_IQC_CHUNK % 8 == 0, "whole 16-B vectors of either type");
 static_assert(SDR_IQC_NSTATE == 12, "mI mQ pII pQQ pIQ dI dQ c1 c2 updates skipped holds");
 
-typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-
 __device__ __forceinline__ float u8f(uint32_t b) { return ((float)b - 128.f) * (1.f / 128.f); }
-
-template <class T>
-__device__ __forceinline__ T wave_sum64(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);   // the same order in every lane
-  return v;
-}
 
 // lane sums -> one record of five values per workgroup, in a fixed order; value k of workgroup b
 // is part[k IQC_MAX_WG + b], so the update's lane-strided loads are contiguous
@@ -82,32 +72,6 @@ __device__ __forceinline__ void block_record(T (&a)[5], T* __restrict__ part) {
     part[threadIdx.x * IQC_MAX_WG + blockIdx.x] = s;
   }
 }
-
-// the chunk [s0, s0 + len) of workgroup blockIdx.x as head samples, 16-B vectors and tail samples
-template <int ES>
-struct Chunk {
-  const char* p;       // the chunk's first sample
-  int64_t len, nv;     // samples; whole 16-B vectors
-  int head, tail;      // samples before the first vector (< 16 / ES) and after the last
-  __device__ __forceinline__ Chunk(const void* iq, int64_t n, int64_t chunk) {
-    constexpr int V = 16 / ES;
-    const int64_t s0 = (int64_t)blockIdx.x * chunk;
-    len = n - s0 < chunk ? n - s0 : chunk;
-    p = reinterpret_cast<const char*>(iq) + s0 * ES;
-    const int mis = (int)((uintptr_t)p & 15);                      // a multiple of ES: iq is aligned to one sample
-    const int64_t h = mis ? (16 - mis) / ES : 0;
-    head = (int)(h < len ? h : len);
-    nv = (len - head) / V;
-    tail = (int)(len - head - nv * V);
-  }
-  __device__ __forceinline__ const u4* vec() const { return reinterpret_cast<const u4*>(p + (int64_t)head * ES); }
-  // the sample this thread takes alone, if any: k = 0 head, k = 1 tail
-  __device__ __forceinline__ const char* single(int k) const {
-    const int t = threadIdx.x;
-    if (k == 0) return t < head ? p + (int64_t)t * ES : nullptr;
-    return t < tail ? p + (head + nv * (16 / ES) + t) * ES : nullptr;
-  }
-};
 
 template <bool U8>
 __global__ __launch_bounds__(IQC_THREADS) void iqc_moments_kernel(const void* __restrict__ iq, int64_t n, int64_t chunk,
@@ -431,9 +395,8 @@ int sdr_iqc_process_dev(sdr_iqc* d, const void* iq, int64_t n, float* out, int e
   if (timing) HIP_TRY(hipEventRecord(d->ev[0], c->stream));
   if (estimate) {
     // at most IQC_MAX_WG chunks of whole 16-B vectors, none shorter than SDR_IQC_CHUNK but the last
-    int64_t chunk = ceil_div(ceil_div(n, IQC_MAX_WG), 8) * 8;
-    chunk = std::max<int64_t>(chunk, SDR_IQC_CHUNK);
-    const int nwg = (int)ceil_div(n, chunk);
+    int64_t chunk;
+    const int nwg = chunks_of(n, SDR_IQC_CHUNK, IQC_MAX_WG, &chunk);
     if (u8) hipLaunchKernelGGL(iqc_moments_kernel<true>, dim3(nwg), dim3(IQC_THREADS), 0, c->stream, iq, n, chunk, d->part);
     else hipLaunchKernelGGL(iqc_moments_kernel<false>, dim3(nwg), dim3(IQC_THREADS), 0, c->stream, iq, n, chunk, d->part);
     HIP_TRY(hipGetLastError());
