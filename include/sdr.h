@@ -751,6 +751,76 @@ int  sdr_rspec_process_dev(sdr_rspec* rspec, const float* x, int64_t n, int64_t 
 int  sdr_rspec_run(sdr_rspec* rspec, const float* x_host, int64_t n, int64_t in_stride,
                    float* out_host, int64_t out_stride);                         /* sync */
 
+/* ---- modulation meter of rows of real samples (a receiver's demodulated or audio rows) -------
+ * What a modulation monitor shows of each stream, taken from the rows where the receiver left
+ * them: peaks, sums for the mean and the power, the share of samples beyond a limit, and the
+ * histogram of the half-spans of consecutive windows (a 50 ms peak hold).  The reference has no
+ * such stage; the definition is rtsdr.RowMeterModel (rowmeter.py).  Per stream, carried from call
+ * to call until sdr_rmeter_reset:
+ *   a sample is finite or not; a non-finite sample counts in nonfinite and nowhere else.
+ *   the call: n finite samples; nonfinite; over, the finite samples with |x| > limit (f32); max and
+ *   min (-inf / +inf without a finite sample); sum = sum f64(x) and sumsq = sum f64(x)^2, f64 sums
+ *   in the kernels' fixed order; windows, the windows completed by the call.
+ *   the totals: calls and the sums, maxima and minima of the calls' values; empty_windows.
+ *   windows: the stream -- every sample, counted by a 64-bit position -- is cut into consecutive
+ *   windows of `window` samples across calls.  A window that completes with a finite sample in it
+ *   adds one to hist[min(nbins - 1, floor(f32(f32(f32(max - min) 0.5f) scale)))], max and min over
+ *   its finite samples; one without counts in empty_windows.  wcount, wmax, wmin: the unfinished
+ *   window.
+ * Two launches per call (csrc/rmeter.hip), no host synchronisation, no atomics: the same calls give
+ * the same bits.  The reduce launch cuts every row at the window boundaries: with window >=
+ * SDR_RMETER_SEG a window is ceil(window / SDR_RMETER_CHUNK) equal chunks, one workgroup each; below
+ * it a chunk is SDR_RMETER_CHUNK / window whole windows, one wave a window.  The fold launch is one
+ * wave a stream.  sdr_rmeter_process_dev: async; row s starts s stride floats into rows; rows at
+ * any 4-byte alignment; the stride - n floats between rows are never read; 1 <= n <= 2^31 - 1; all
+ * offsets are 64-bit.  It may grow the object's work arrays, which waits for the stream once.
+ * sdr_rmeter_run: host rows stride floats apart.  sdr_rmeter_records, _hist and _windows
+ * synchronise.  sdr_rmeter_windows: the (min, max) pairs of the windows the latest call completed,
+ * in order, stream s at host + 2 s cap, at most cap of them; counts[s] (may be NULL) is how many
+ * the call completed; a window without a finite sample reads (+inf, -inf).  sdr_rmeter_state_dev:
+ * the device arrays, for a consumer on the stream.
+ * SDR_EINVAL (before any device work): NULL pointers, nstreams outside 1 .. SDR_RMETER_MAX_STREAMS,
+ * window outside [SDR_RMETER_MIN_WINDOW, SDR_RMETER_MAX_WINDOW], nbins outside 1 ..
+ * SDR_RMETER_MAX_BINS, a scale that is not finite and positive, a NaN limit, n outside
+ * [1, 2^31 - 1], stride < n with more than one stream, a pointer not aligned to 4 B, cap < 0.  No
+ * host fallback. */
+#define SDR_RMETER_MAX_STREAMS 4096
+#define SDR_RMETER_MIN_WINDOW 64
+#define SDR_RMETER_MAX_WINDOW 16777216
+#define SDR_RMETER_MAX_BINS 1024
+#define SDR_RMETER_CHUNK 16384
+#define SDR_RMETER_SEG 4096
+typedef struct sdr_rmeter_params {
+  int64_t window;   /* samples of a window */
+  int nbins;        /* histogram bins per stream */
+  float scale;      /* bins per unit of the row */
+  float limit;      /* |x| beyond it counts in over */
+} sdr_rmeter_params;
+typedef struct sdr_rmeter_record {
+  int64_t n, nonfinite, over, windows;                                    /* the latest call */
+  double sum, sumsq;
+  float max, min;
+  int64_t calls, total_n, total_nonfinite, total_over, total_windows, empty_windows;
+  double total_sum, total_sumsq;
+  float total_max, total_min;
+  int64_t wcount;                                                         /* the unfinished window */
+  float wmax, wmin;
+} sdr_rmeter_record;
+typedef struct sdr_rmeter sdr_rmeter;
+int  sdr_rmeter_create(sdr_ctx* ctx, int nstreams, const sdr_rmeter_params* params, sdr_rmeter** out);
+void sdr_rmeter_destroy(sdr_rmeter* rm);
+int  sdr_rmeter_reset(sdr_rmeter* rm);                                                       /* async */
+int  sdr_rmeter_process_dev(sdr_rmeter* rm, const float* rows, int64_t stride, int64_t n);   /* async */
+int  sdr_rmeter_run(sdr_rmeter* rm, const float* rows_host, int64_t stride, int64_t n);      /* sync */
+int  sdr_rmeter_records(sdr_rmeter* rm, sdr_rmeter_record* host /* [nstreams] */);           /* synchronises */
+int  sdr_rmeter_hist(sdr_rmeter* rm, uint64_t* host /* [nstreams][nbins] */);                /* synchronises */
+int  sdr_rmeter_windows(sdr_rmeter* rm, float* host /* [nstreams][cap][2] */, int64_t cap, int64_t* counts /* [nstreams] */);
+int  sdr_rmeter_state_dev(sdr_rmeter* rm, const sdr_rmeter_record** dev, const uint64_t** hist_dev);
+/* per-launch timing of the last call (HIP events around the two launches, on the context stream):
+ * reduce, fold; ms: 2 floats.  Keep it off in measured loops. */
+int  sdr_rmeter_set_timing(sdr_rmeter* rm, int on);
+int  sdr_rmeter_stage_ms(sdr_rmeter* rm, float* ms);
+
 /* ---- spectral diagnostics -----------------------------------------
  * Bartlett PSD, model/fmSupportLib.py:66-140 (estimatePSD; the C++ src/fourier.cpp:36-110
  * advances sample and list positions by the same nfft/2 and is not the parity target):

@@ -32,7 +32,10 @@ the capture's stages, the correction of a direct-conversion front end's DC offse
 IqBalance (host, numpy f64: the specification) and IqCorrector (device); and in front of that, the
 raw formats wideband front ends write (signed 8- and 16-bit IQ, narrower ADC codes in 16-bit words)
 as the float32 capture, with a level meter of the ADC's codes: ingest_model, capture_format (host,
-numpy: the specification) and CaptureIngest (device).
+numpy: the specification) and CaptureIngest (device); and behind the receiver, the modulation
+meter of its demodulated and audio rows (peak deviation, multiplex power, carrier offset, the
+histogram of 50 ms peak holds): RowMeterModel, row_meter_model, modulation_report, mpx_levels (host,
+numpy: the specification) and RowMeter (device, Receiver.modulation_meter, Receiver.audio_meter).
 See DESIGN.md and INTEGRATION.md.
 """
 from . import design, synth  # noqa: F401
@@ -40,13 +43,14 @@ from ._lib import (SDR_IQ_F32, SDR_IQ_S8, SDR_IQ_S16, SDR_IQ_U8, SDR_PRE_MIX, SD
                    DeviceBuffer, SdrError, SdrUnavailable, Timer, device_count, device_info, get_context,
                    load_library)
 from .blocks import (BlendControl, BlendParams, BlendState, CaptureIngest, Channelizer, FilterBank, IqCorrector, MonoBlockProcessor, MpxQuality, RdsBlockProcessor, RdsCarrierBank, RdsClockBank, RdsLinkBank, RdsLinkLayer, RdsSyncBank,  # noqa: F401
-                     Receiver, RowResampler, RowSpectrum, Spectrum, StereoBlockProcessor, find_channels, mpx_quality, rds_groups,
+                     Receiver, RowMeter, RowResampler, RowSpectrum, Spectrum, StereoBlockProcessor, find_channels, mpx_quality, rds_groups,
                      spectrum_rows)
 from .rdssync import RdsBlockSync, RdsProgramme  # noqa: F401
 from .rdsclock import RdsSymbolClock  # noqa: F401
 from .rdscarrier import RdsCarrierPhase  # noqa: F401
 from .iqbalance import IqBalance, IqState  # noqa: F401
 from .capture import IngestMeter, capture_format, ingest_model  # noqa: F401
+from .rowmeter import ModulationReport, MpxLevels, RowMeterModel, RowMeterRecord, modulation_report, mpx_levels, row_meter_model  # noqa: F401
 from .design import impulseResponseRootRaisedCosine, my_filterImpulseResponse  # noqa: F401
 from .dsp import (DFT, MonoState, estimatePSD, fm_mono_range, fm_mono_streams, split_halo, fmDemodArctan, fmPll, lfilter, lfilter_decim,  # noqa: F401
                   audio_blend_dev, audio_out, deemphasis, iir1, mono_block, my_convoloution, resample, rf_frontend_block)

@@ -37,6 +37,7 @@ SDR_RDS_CLOCK_NSTATE = 10
 SDR_RDS_CARRIER_NSTATE = 7
 SDR_IQC_NSTATE, SDR_IQC_CHUNK = 12, 4096   # the corrector of the capture (include/sdr.h sdr_iqc_*)
 SDR_INGEST_CHUNK = 4096                           # capture ingest (include/sdr.h sdr_ingest_*)
+SDR_RMETER_CHUNK, SDR_RMETER_SEG = 16384, 4096     # the rows' modulation meter (include/sdr.h sdr_rmeter_*)
 PLL_STATS = ("recurrences", "spec_r0", "spec_r1", "spec_r2", "sequential", "long_guessed", "long_chained",
              "long_maxgap", "long_stops", "long_tail", "long_linear")
 
@@ -140,6 +141,17 @@ SIGNATURES = {
     "sdr_ingest_run": (_i32, [_vp, _vp, _i64, _vp]),
     "sdr_ingest_meter_get": (_i32, [_vp, _vp]),
     "sdr_ingest_meter_dev": (_i32, [_vp, _c.POINTER(_vp)]),
+    "sdr_rmeter_create": (_i32, [_vp, _i32, _vp, _c.POINTER(_vp)]),
+    "sdr_rmeter_destroy": (None, [_vp]),
+    "sdr_rmeter_reset": (_i32, [_vp]),
+    "sdr_rmeter_process_dev": (_i32, [_vp, _vp, _i64, _i64]),
+    "sdr_rmeter_run": (_i32, [_vp, _vp, _i64, _i64]),
+    "sdr_rmeter_records": (_i32, [_vp, _vp]),
+    "sdr_rmeter_hist": (_i32, [_vp, _vp]),
+    "sdr_rmeter_windows": (_i32, [_vp, _vp, _i64, _vp]),
+    "sdr_rmeter_state_dev": (_i32, [_vp, _c.POINTER(_vp), _c.POINTER(_vp)]),
+    "sdr_rmeter_set_timing": (_i32, [_vp, _i32]),
+    "sdr_rmeter_stage_ms": (_i32, [_vp, _fp]),
     "sdr_iqc_create": (_i32, [_vp, _i32, _vp, _c.POINTER(_vp)]),
     "sdr_iqc_destroy": (None, [_vp]),
     "sdr_iqc_reset": (_i32, [_vp]),

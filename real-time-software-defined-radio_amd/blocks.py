@@ -26,6 +26,7 @@ from . import _lib
 from . import capture
 from . import design
 from . import iqbalance
+from . import rowmeter
 from ._lib import RX_FILTERS, RX_OUTPUTS, SDR_IQ_F32, SDR_IQ_U8, SDR_RX_AUDIO, SDR_RX_RDS, SDR_RX_STEREO, check, f64p
 from .dsp import _taps
 
@@ -415,6 +416,26 @@ class Receiver(_Handle):
         kw.setdefault("ctx", self.ctx)
         nfft = int(nfft)
         return RowSpectrum(self.S, nfft, design.AUDIO_FS, hop=nfft // 2 if hop is None else hop, navg=navg, **kw)
+
+    def modulation_meter(self, window_s: float = 0.05, bin_hz: float = 1e3, limit_hz: float = 75e3, nbins: int = 128, **kw) -> "RowMeter":
+        """A RowMeter sized to this receiver's "demod" rows (radians per sample at design.AUDIO_FS):
+        windows of round(window_s AUDIO_FS) samples, histogram bins of bin_hz of peak deviation
+        (scale = float32(AUDIO_FS / (2 pi bin_hz))), over-deviation beyond limit_hz (limit =
+        float32(2 pi limit_hz / AUDIO_FS)).  Feed it with meter.process_rx(receiver) after a block and
+        read meter.records() with modulation_report."""
+        kw.setdefault("ctx", self.ctx)
+        fs = design.AUDIO_FS
+        return RowMeter(self.S, int(round(window_s * fs)), nbins=nbins, scale=np.float32(fs / (2 * np.pi * bin_hz)),
+                        limit=np.float32(2 * np.pi * limit_hz / fs), **kw)
+
+    def audio_meter(self, name: str = "audio", window_s: float = 0.05, scale: float = 128.0, limit: float = 1.0, nbins: int = 128, **kw) -> "RowMeter":
+        """The same object on an audio row (`name`: "audio", "left", "right" or their _de forms):
+        windows of round(window_s x the row's rate) samples, `scale` bins per unit of amplitude; peak,
+        RMS (from sum and sumsq) and dead air (windows in bin 0) per stream.  Feed it with
+        meter.process_rx(receiver, name)."""
+        kw.setdefault("ctx", self.ctx)
+        fs = design.AUDIO_FS * self._length(name) / self._length("demod")
+        return RowMeter(self.S, int(round(window_s * fs)), nbins=nbins, scale=scale, limit=limit, **kw)
 
     def set_timing(self, on: bool = True):
         """Record HIP events between the receiver's launches (stage_ms)."""
@@ -1547,6 +1568,126 @@ def mpx_quality(power, fs: float = 240e3, min_pilot_db: float = 15.0, min_rds_db
     pilot, floor = ratio_db(MPX_PILOT_BAND, MPX_PILOT_GUARD)
     rds, _ = ratio_db(MPX_RDS_BAND, MPX_RDS_GUARD)
     return MpxQuality(pilot, rds, floor, pilot >= float(min_pilot_db), rds >= float(min_rds_db))
+
+
+class _RmeterParamsC(ctypes.Structure):                          # include/sdr.h sdr_rmeter_params
+    _fields_ = [("window", ctypes.c_int64), ("nbins", ctypes.c_int), ("scale", ctypes.c_float), ("limit", ctypes.c_float)]
+
+
+class _RmeterRecordC(ctypes.Structure):                          # include/sdr.h sdr_rmeter_record
+    _fields_ = [(k, {np.int64: ctypes.c_int64, np.float64: ctypes.c_double, np.float32: ctypes.c_float}[rowmeter.field_dtype(k)])
+                for k in rowmeter.FIELDS]
+
+
+class RowMeter(_Handle):
+    """The modulation meter of `nstreams` rows of real float32 samples on the GPU (sdr_rmeter,
+    csrc/rmeter.hip) -- a Receiver's "demod" or audio rows, read where the receiver left them.  Per
+    stream and carried from call to call: the call's and the totals' finite / non-finite / over-limit
+    counts, max, min, float64 sum and sum of squares, and the histogram (`nbins` bins, `scale` bins
+    per unit of the row) of the half-spans (max - min) / 2 of consecutive windows of `window`
+    samples, cut across calls by a 64-bit stream position.  Two launches per call, nothing returns to
+    the host until records(), hist() or windows() is asked; the same calls give the same bits.
+
+    The rule is rtsdr.RowMeterModel's (rowmeter.py): integers, peaks, histogram and windows equal it
+    exactly, the float64 sums within the summation bound.  modulation_report reads a record.  The
+    arguments are checked before a context exists; the device object is made at the first call that
+    needs it."""
+
+    CHUNK, SEG = _lib.SDR_RMETER_CHUNK, _lib.SDR_RMETER_SEG      # a window from SEG samples on is cut into chunks of at most CHUNK
+    MAX_N = rowmeter.MAX_N
+    _prefix = "sdr_rmeter"
+
+    def __init__(self, nstreams: int, window: int, nbins: int = 128, scale: float = 1.0, limit: float = np.inf, ctx=None):
+        self.nstreams, self.window, self.nbins, self.scale, self.limit = rowmeter.check_params(nstreams, window, nbins, scale, limit)
+        self._ctx = ctx
+
+    def _open(self):
+        if self.handle is None:
+            self.ctx = self._ctx if self._ctx is not None else _lib.get_context()
+            self.lib = self.ctx.lib
+            h = ctypes.c_void_p()
+            prm = _RmeterParamsC(self.window, self.nbins, float(self.scale), float(self.limit))
+            check(self.lib.sdr_rmeter_create(self.ctx.handle, self.nstreams, ctypes.byref(prm), ctypes.byref(h)), "sdr_rmeter_create")
+            self.handle = h
+        return self.handle
+
+    def process_dev(self, ptr: int, stride: int, n: int):
+        """n samples per row at device pointer ptr, rows stride floats apart (the floats between rows
+        are never read; any 4-byte alignment); async on the context stream."""
+        ptr, stride, n = int(ptr or 0), int(stride), int(n)
+        if not ptr:
+            raise ValueError("ptr is NULL")
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError(f"n={n} outside [1, 2^31 - 1]")
+        if self.nstreams > 1 and stride < n:
+            raise ValueError(f"stride={stride} < n={n}")
+        if ptr % 4:
+            raise ValueError("ptr must be aligned to 4 B")
+        h = self._open()
+        check(self.lib.sdr_rmeter_process_dev(h, ptr, stride, n), "sdr_rmeter_process_dev")
+
+    def process_rx(self, receiver: "Receiver", name: str = "demod"):
+        """The receiver's latest rows of output `name`, read in place (looked up at every call: a
+        pipelined receiver alternates its row sets)."""
+        if receiver.S != self.nstreams:
+            raise ValueError(f"the receiver has {receiver.S} streams, the meter {self.nstreams}")
+        ptr, stride, n = receiver.output_ptr(name)
+        self.process_dev(ptr, stride, n)
+
+    def run(self, rows_host):
+        """(nstreams, n) real samples from the host; synchronous (sdr_rmeter_run)."""
+        x = np.ascontiguousarray(rowmeter.as_rows(rows_host, self.nstreams))
+        h = self._open()
+        check(self.lib.sdr_rmeter_run(h, x.ctypes.data, x.shape[1], x.shape[1]), "sdr_rmeter_run")
+
+    def records(self) -> "rowmeter.RowMeterRecord":
+        """The state after the latest call, an array entry per stream (sdr_rmeter_records; synchronises)."""
+        raw = (_RmeterRecordC * self.nstreams)()
+        h = self._open()
+        check(self.lib.sdr_rmeter_records(h, ctypes.byref(raw)), "sdr_rmeter_records")
+        return rowmeter.RowMeterRecord(*(np.array([getattr(r, k) for r in raw], dtype=rowmeter.field_dtype(k)) for k in rowmeter.FIELDS))
+
+    def hist(self) -> np.ndarray:
+        """uint64[nstreams, nbins] (sdr_rmeter_hist; synchronises)."""
+        out = np.empty((self.nstreams, self.nbins), dtype=np.uint64)
+        h = self._open()
+        check(self.lib.sdr_rmeter_hist(h, out.ctypes.data), "sdr_rmeter_hist")
+        return out
+
+    def windows(self) -> np.ndarray:
+        """float32[nstreams, windows, 2]: (min, max) of the windows the latest call completed, in
+        order; (+inf, -inf) for one without a finite sample (sdr_rmeter_windows; synchronises)."""
+        h = self._open()
+        counts = np.zeros(self.nstreams, dtype=np.int64)
+        check(self.lib.sdr_rmeter_windows(h, None, 0, counts.ctypes.data), "sdr_rmeter_windows")
+        out = np.empty((self.nstreams, int(counts[0]), 2), dtype=np.float32)
+        if out.size:
+            check(self.lib.sdr_rmeter_windows(h, out.ctypes.data, out.shape[1], None), "sdr_rmeter_windows")
+        return out
+
+    def state_ptr(self):
+        """(record pointer, histogram pointer): the device arrays of struct sdr_rmeter_record [nstreams]
+        and uint64 [nstreams][nbins] (sdr_rmeter_state_dev)."""
+        p, q = ctypes.c_void_p(), ctypes.c_void_p()
+        h = self._open()
+        check(self.lib.sdr_rmeter_state_dev(h, ctypes.byref(p), ctypes.byref(q)), "sdr_rmeter_state_dev")
+        return p.value, q.value
+
+    def reset(self):
+        """Zero the records, the histogram and the stream position (async)."""
+        h = self._open()
+        check(self.lib.sdr_rmeter_reset(h), "sdr_rmeter_reset")
+
+    def set_timing(self, on: bool = True):
+        """Record HIP events around the two launches of each call (stage_ms)."""
+        h = self._open()
+        check(self.lib.sdr_rmeter_set_timing(h, int(bool(on))), "sdr_rmeter_set_timing")
+
+    def stage_ms(self) -> dict:
+        """GPU time of the last call's launches (set_timing(True) first): reduce, fold."""
+        ms = np.zeros(2, dtype=np.float32)
+        check(self.lib.sdr_rmeter_stage_ms(self.handle, ms.ctypes.data_as(_lib._fp)), "sdr_rmeter_stage_ms")
+        return dict(zip(("reduce", "fold"), (float(v) for v in ms)))
 
 
 class _BlendParamsC(ctypes.Structure):                           # include/sdr.h sdr_blend_params

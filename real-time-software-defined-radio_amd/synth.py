@@ -153,6 +153,23 @@ def fm_iq(n_complex: int, seed: int = 0, fs: float = FS, snr_db: float = 30.0, c
     return out
 
 
+def fm_mpx(n: int, fs: float = 240e3, rds: bool = False, seed: int = 0) -> np.ndarray:
+    """The multiplex fm_iq modulates, as a float64 share of the 75 kHz peak deviation at sample rate
+    fs (pilot at 19 kHz): 2 pi 75e3 fm_mpx / fs is the ideal "demod" row in radians per sample.
+    rds adds the 57 kHz subcarrier with random symbols drawn from `seed`; without it the row is
+    periodic in 2 ms (1 kHz, 2.5 kHz, 19 kHz, 38 kHz), which is what a meter's figures are pinned on."""
+    t = np.arange(n, dtype=np.float64) / fs
+    left = np.sin(2 * np.pi * 1e3 * t)
+    right = 0.8 * np.sin(2 * np.pi * 2.5e3 * t)
+    mpx = (0.45 * (left + right) / 2 + 0.1 * np.cos(2 * np.pi * 19e3 * t)
+           + 0.45 * (left - right) / 2 * np.cos(2 * np.pi * 38e3 * t))
+    if rds:
+        sym_len = fs / 2375.0
+        symbols = np.random.default_rng(seed).choice(np.array([-1.0, 1.0]), size=int(np.ceil(n / sym_len)) + 2)
+        mpx = mpx + 0.05 * symbols[(np.arange(n) / sym_len).astype(np.int64)] * np.cos(2 * np.pi * 57e3 * t)
+    return mpx
+
+
 def to_u8(iq: np.ndarray) -> np.ndarray:
     """round(127 * x / max|x| + 128), the rtl_sdr-style byte stream."""
     peak = float(np.max(np.abs(iq))) or 1.0
