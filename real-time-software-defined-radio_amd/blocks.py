@@ -65,6 +65,66 @@ class _Handle:
             pass
 
 
+class _LazyHandle(_Handle):
+    """A libsdr object made at the first call that needs it: the constructor checks its arguments
+    without a context and keeps `ctx` in _ctx (None: the default context); _create_args() gives
+    what <prefix>_create takes between the context and the handle."""
+
+    _ctx = None
+
+    def _open(self):
+        if self.handle is None:
+            self.ctx = self._ctx if self._ctx is not None else _lib.get_context()
+            self.lib = self.ctx.lib
+            h, name = ctypes.c_void_p(), f"{self._prefix}_create"
+            check(getattr(self.lib, name)(self.ctx.handle, *self._create_args(), ctypes.byref(h)), name)
+            self.handle = h
+        return self.handle
+
+    def _do(self, op, *args):
+        self._open()
+        super()._do(op, *args)
+
+    def _ptr_out(self, op, count=1):
+        """The device pointer <prefix>_<op> hands out (count > 1: a tuple of them)."""
+        p = [ctypes.c_void_p() for _ in range(count)]
+        self._do(op, *(ctypes.byref(q) for q in p))
+        return p[0].value if count == 1 else tuple(q.value for q in p)
+
+
+class _Timed:
+    """HIP events between the launches of each call, for an object whose C prefix has _set_timing
+    and _stage_ms: _STAGES names the launches."""
+
+    _STAGES = ()
+
+    def set_timing(self, on: bool = True):
+        """Record HIP events between the object's launches (stage_ms); off in measured loops."""
+        self._do("set_timing", int(bool(on)))
+
+    def stage_ms(self) -> dict:
+        """GPU milliseconds per launch of the last timed call (set_timing(True) first), by _STAGES."""
+        ms = (ctypes.c_float * len(self._STAGES))()
+        self._do("stage_ms", ms)
+        return dict(zip(self._STAGES, (float(v) for v in ms)))
+
+
+def _check_capture_call(name, ptr, es, n, out_ptr, in_place_ok, owner):
+    """The call rule of a pass over a capture block (CaptureIngest, IqCorrector): n complex samples
+    of es bytes at device pointer `<name>_ptr` to n complex float32 at out_ptr, which may be the
+    same pointer where in_place_ok (`owner` says for whom).  Returns (ptr, n, out_ptr) as ints."""
+    n, ptr, out_ptr = int(n), int(ptr or 0), int(out_ptr or 0)
+    if not ptr or not out_ptr:
+        raise ValueError(f"{name}_ptr or out_ptr is NULL")
+    if not 1 <= n <= capture.MAX_N:
+        raise ValueError(f"n={n} outside [1, 2^31 - 1]")
+    if ptr % es or out_ptr % 8:
+        raise ValueError(f"{name}_ptr must be aligned to one complex sample ({es} B) and out_ptr to 8 B")
+    if ptr < out_ptr + 8 * n and out_ptr < ptr + es * n and not (in_place_ok and ptr == out_ptr):
+        raise ValueError(f"{name} and out overlap (only out_ptr == {name}_ptr of {owner} may)")
+    return ptr, n, out_ptr
+
+
 class _Stream(_Handle):
     """A block that carries a history and a stream position from call to call."""
 
@@ -150,7 +210,7 @@ def _is_u8(iq_dtype):
     return dt == np.uint8
 
 
-class Receiver(_Handle):
+class Receiver(_Timed, _Handle):
     """`nstreams` independent FM streams through the block receiver (sdr_rx).
 
     Each call to process() takes one block of every stream: an (nstreams, 2*block) array of
@@ -175,6 +235,7 @@ class Receiver(_Handle):
     blend_state() reads the quality and gains back."""
 
     _prefix = "sdr_rx"
+    _STAGES = _lib.RX_STAGES                                     # stage_ms: the stages of the last block
 
     def __init__(self, nstreams: int, block_complex: int, *, mono: bool = True, stereo: bool = False,
                  rds: bool = False, iq_dtype=np.uint8, rf_coeff=None, audio_coeff=None, stereo_taps: int = 151,
@@ -436,16 +497,6 @@ class Receiver(_Handle):
         kw.setdefault("ctx", self.ctx)
         fs = design.AUDIO_FS * self._length(name) / self._length("demod")
         return RowMeter(self.S, int(round(window_s * fs)), nbins=nbins, scale=scale, limit=limit, **kw)
-
-    def set_timing(self, on: bool = True):
-        """Record HIP events between the receiver's launches (stage_ms)."""
-        check(self.lib.sdr_rx_set_timing(self.handle, int(bool(on))), "sdr_rx_set_timing")
-
-    def stage_ms(self) -> dict:
-        """GPU time per stage of the last block (set_timing(True) first): _lib.RX_STAGES."""
-        ms = np.zeros(len(_lib.RX_STAGES), dtype=np.float32)
-        check(self.lib.sdr_rx_stage_ms(self.handle, ms.ctypes.data_as(_lib._fp)), "sdr_rx_stage_ms")
-        return dict(zip(_lib.RX_STAGES, (float(v) for v in ms)))
 
 
 class MonoBlockProcessor:
@@ -896,7 +947,7 @@ class _IngestMeterC(ctypes.Structure):                           # include/sdr.h
                 [(k, ctypes.c_double) for k in ("peak", "sumsq")] + [(k, ctypes.c_int64) for k in ("calls", "total_n", "total_clipped")])
 
 
-class CaptureIngest(_Handle):
+class CaptureIngest(_LazyHandle):
     """The raw bytes of a capture block to the float32 capture on the GPU, with a level meter
     (sdr_ingest, csrc/ingest.hip): the stage in front of IqCorrector.  `fmt` is 'cu8', 'cs8', 'cs16'
     or 'cf32' (or numpy's uint8, int8, int16, float32; capture_format maps file and SigMF names);
@@ -924,30 +975,13 @@ class CaptureIngest(_Handle):
         self.es = 2 * capture.FORMATS[self.fmt][0].itemsize      # bytes of a complex sample
         self._ctx = ctx
 
-    def _open(self):
-        if self.handle is None:
-            self.ctx = self._ctx if self._ctx is not None else _lib.get_context()
-            self.lib = self.ctx.lib
-            h = ctypes.c_void_p()
-            prm = _IngestParamsC(self.bits, int(self.swap), int(self.metered))
-            check(self.lib.sdr_ingest_create(self.ctx.handle, self._DTYPES[self.fmt], ctypes.byref(prm), ctypes.byref(h)), "sdr_ingest_create")
-            self.handle = h
-        return self.handle
+    def _create_args(self):
+        return self._DTYPES[self.fmt], ctypes.byref(_IngestParamsC(self.bits, int(self.swap), int(self.metered)))
 
     def process_dev(self, raw_ptr: int, n: int, out_ptr: int):
         """n complex samples of the format at device pointer raw_ptr -> n complex float32 at out_ptr;
         async on the context stream."""
-        n, raw_ptr, out_ptr = int(n), int(raw_ptr or 0), int(out_ptr or 0)
-        if not raw_ptr or not out_ptr:
-            raise ValueError("raw_ptr or out_ptr is NULL")
-        if not 1 <= n <= self.MAX_N:
-            raise ValueError(f"n={n} outside [1, 2^31 - 1]")
-        if raw_ptr % self.es or out_ptr % 8:
-            raise ValueError(f"raw_ptr must be aligned to one complex sample ({self.es} B) and out_ptr to 8 B")
-        if raw_ptr < out_ptr + 8 * n and out_ptr < raw_ptr + self.es * n and not (self.fmt == "cf32" and raw_ptr == out_ptr):
-            raise ValueError("raw and out overlap (only out_ptr == raw_ptr of a cf32 ingest may)")
-        h = self._open()
-        check(self.lib.sdr_ingest_process_dev(h, raw_ptr, n, out_ptr), "sdr_ingest_process_dev")
+        self._do("process_dev", *_check_capture_call("raw", raw_ptr, self.es, n, out_ptr, self.fmt == "cf32", "a cf32 ingest"))
 
     def run(self, raw) -> np.ndarray:
         """A capture block from the host (values of the format's type, raw bytes, or complex64 for
@@ -955,37 +989,31 @@ class CaptureIngest(_Handle):
         raw = capture.as_raw(raw, self.fmt)
         n = raw.size // 2
         out = np.empty(2 * n, dtype=np.float32)
-        h = self._open()
-        check(self.lib.sdr_ingest_run(h, raw.ctypes.data, n, out.ctypes.data), "sdr_ingest_run")
+        self._do("run", raw.ctypes.data, n, out.ctypes.data)
         return out
 
     def meter(self) -> "capture.IngestMeter":
         """The meter of the last call and the totals since the last reset (sdr_ingest_meter_get;
         synchronises)."""
         m = _IngestMeterC()
-        h = self._open()
-        check(self.lib.sdr_ingest_meter_get(h, ctypes.byref(m)), "sdr_ingest_meter_get")
+        self._do("meter_get", ctypes.byref(m))
         return capture.IngestMeter(*(getattr(m, k) for k in capture.IngestMeter._fields))
 
     @property
     def meter_ptr(self) -> int:
         """The device copy of the meter, a struct sdr_ingest_meter (sdr_ingest_meter_dev)."""
-        p = ctypes.c_void_p()
-        h = self._open()
-        check(self.lib.sdr_ingest_meter_dev(h, ctypes.byref(p)), "sdr_ingest_meter_dev")
-        return p.value
+        return self._ptr_out("meter_dev")
 
     def reset(self):
         """Zero the meter and its totals (async)."""
-        h = self._open()
-        check(self.lib.sdr_ingest_reset(h), "sdr_ingest_reset")
+        self._do("reset")
 
 
 class _IqcParamsC(ctypes.Structure):                             # include/sdr.h sdr_iqc_params
     _fields_ = [("rate", ctypes.c_double), ("dc", ctypes.c_int), ("balance", ctypes.c_int)]
 
 
-class IqCorrector(_Handle):
+class IqCorrector(_Timed, _LazyHandle):
     """IQ imbalance and DC offset correction of a capture block on the GPU (sdr_iqc, csrc/iqc.hip):
     the stage in front of Spectrum, Channelizer and FilterBank.  A direct-conversion front end's Q
     branch has a slightly different gain and is not quite 90 degrees from I, so every station at +f
@@ -1006,38 +1034,21 @@ class IqCorrector(_Handle):
     CHUNK = _lib.SDR_IQC_CHUNK                                   # samples of a workgroup's chunk (at least)
     MAX_N = 2 ** 31 - 1
     _prefix = "sdr_iqc"
+    _STAGES = ("moments", "update", "apply")                     # stage_ms: the last call made with an estimate
 
     def __init__(self, iq_dtype=np.float32, rate: float = iqbalance.DEFAULT_RATE, dc: bool = True, balance: bool = True, ctx=None):
         self.u8 = _is_u8(iq_dtype)
         self.rate, self.dc, self.balance = iqbalance.check_rate(rate), bool(dc), bool(balance)
         self._ctx = ctx
 
-    def _open(self):
-        if self.handle is None:
-            self.ctx = self._ctx if self._ctx is not None else _lib.get_context()
-            self.lib = self.ctx.lib
-            h = ctypes.c_void_p()
-            prm = _IqcParamsC(self.rate, int(self.dc), int(self.balance))
-            check(self.lib.sdr_iqc_create(self.ctx.handle, SDR_IQ_U8 if self.u8 else SDR_IQ_F32, ctypes.byref(prm), ctypes.byref(h)),
-                  "sdr_iqc_create")
-            self.handle = h
-        return self.handle
+    def _create_args(self):
+        return SDR_IQ_U8 if self.u8 else SDR_IQ_F32, ctypes.byref(_IqcParamsC(self.rate, int(self.dc), int(self.balance)))
 
     def process_dev(self, iq_ptr: int, n: int, out_ptr: int, estimate: bool = True):
         """n complex samples at device pointer iq_ptr -> n corrected complex float32 at out_ptr;
         async on the context stream."""
-        n, iq_ptr, out_ptr = int(n), int(iq_ptr or 0), int(out_ptr or 0)
-        es = 2 if self.u8 else 8
-        if not iq_ptr or not out_ptr:
-            raise ValueError("iq_ptr or out_ptr is NULL")
-        if not 1 <= n <= self.MAX_N:
-            raise ValueError(f"n={n} outside [1, 2^31 - 1]")
-        if iq_ptr % es or out_ptr % 8:
-            raise ValueError(f"iq_ptr must be aligned to one complex sample ({es} B) and out_ptr to 8 B")
-        if iq_ptr < out_ptr + 8 * n and out_ptr < iq_ptr + es * n and not (not self.u8 and iq_ptr == out_ptr):
-            raise ValueError("iq and out overlap (only out_ptr == iq_ptr of a float32 corrector may)")
-        h = self._open()
-        check(self.lib.sdr_iqc_process_dev(h, iq_ptr, n, out_ptr, int(bool(estimate))), "sdr_iqc_process_dev")
+        args = _check_capture_call("iq", iq_ptr, 2 if self.u8 else 8, n, out_ptr, not self.u8, "a float32 corrector")
+        self._do("process_dev", *args, int(bool(estimate)))
 
     def run(self, iq, estimate: bool = True) -> np.ndarray:
         """n complex samples from the host (interleaved f32 / u8, or complex for a float32 object)
@@ -1047,16 +1058,14 @@ class IqCorrector(_Handle):
         if not 1 <= n <= self.MAX_N:
             raise ValueError(f"n={n} outside [1, 2^31 - 1]")
         out = np.empty(2 * n, dtype=np.float32)
-        h = self._open()
-        check(self.lib.sdr_iqc_run(h, iq.ctypes.data, n, out.ctypes.data, int(bool(estimate))), "sdr_iqc_run")
+        self._do("run", iq.ctypes.data, n, out.ctypes.data, int(bool(estimate)))
         return out
 
     def raw_state(self) -> np.ndarray:
         """The 12 float64 values mI mQ pII pQQ pIQ dI dQ c1 c2 updates skipped holds (sdr_iqc_state;
         synchronises)."""
         out = np.empty(self.NSTATE)
-        h = self._open()
-        check(self.lib.sdr_iqc_state(h, f64p(out)), "sdr_iqc_state")
+        self._do("state", f64p(out))
         return out
 
     def state(self) -> "iqbalance.IqState":
@@ -1067,33 +1076,16 @@ class IqCorrector(_Handle):
     def set(self, dI: float, dQ: float, c1: float, c2: float):
         """Install coefficients (async); the next estimate replaces them."""
         c = np.array(iqbalance.check_coeffs((dI, dQ, c1, c2)))
-        h = self._open()
-        check(self.lib.sdr_iqc_set(h, f64p(c)), "sdr_iqc_set")
+        self._do("set", f64p(c))
 
     def reset(self):
         """Back to the state after creation (async)."""
-        h = self._open()
-        check(self.lib.sdr_iqc_reset(h), "sdr_iqc_reset")
-
-    def set_timing(self, on: bool = True):
-        """HIP events between the launches of each call (sdr_iqc_set_timing); off in measured loops."""
-        h = self._open()
-        check(self.lib.sdr_iqc_set_timing(h, int(bool(on))), "sdr_iqc_set_timing")
-
-    def stage_ms(self) -> dict:
-        """{moments, update, apply}: milliseconds of the last call made with an estimate (sdr_iqc_stage_ms)."""
-        ms = (ctypes.c_float * 3)()
-        h = self._open()
-        check(self.lib.sdr_iqc_stage_ms(h, ms), "sdr_iqc_stage_ms")
-        return dict(zip(("moments", "update", "apply"), (float(v) for v in ms)))
+        self._do("reset")
 
     @property
     def coeffs_ptr(self) -> int:
         """The device array of four float64 dI dQ c1 c2 (sdr_iqc_coeffs_dev)."""
-        p = ctypes.c_void_p()
-        h = self._open()
-        check(self.lib.sdr_iqc_coeffs_dev(h, ctypes.byref(p)), "sdr_iqc_coeffs_dev")
-        return p.value
+        return self._ptr_out("coeffs_dev")
 
 
 class Channelizer(_DecimBlock):
@@ -1302,7 +1294,7 @@ def spectrum_rows(n: int, nfft: int, hop: int, navg: int):
     return nseg, rows
 
 
-class Spectrum(_Handle):
+class Spectrum(_LazyHandle):
     """The spectrum / waterfall of a wideband IQ capture on the GPU (sdr_spec, csrc/spectrum.hip):
     Welch periodogram rows of the buffer Channelizer / FilterBank read, in place -- which of the
     band's channels carry a station?  With segment s starting at sample s hop and window w,
@@ -1356,15 +1348,8 @@ class Spectrum(_Handle):
         """(nseg, rows) of a call of n samples."""
         return spectrum_rows(n, self.nfft, self.hop, self.navg)
 
-    def _open(self):
-        if self.handle is None:
-            self.ctx = self._ctx if self._ctx is not None else _lib.get_context()
-            self.lib = self.ctx.lib
-            h = ctypes.c_void_p()
-            check(self.lib.sdr_spec_create(self.ctx.handle, self.nfft, f64p(self.window), self.hop, self.navg,
-                                           SDR_IQ_U8 if self.u8 else SDR_IQ_F32, ctypes.byref(h)), "sdr_spec_create")
-            self.handle = h
-        return self.handle
+    def _create_args(self):
+        return self.nfft, f64p(self.window), self.hop, self.navg, SDR_IQ_U8 if self.u8 else SDR_IQ_F32
 
     def process_dev(self, iq_ptr: int, n: int, out_ptr: int, out_stride=None) -> int:
         """n complex samples at device pointer iq_ptr -> rows of nfft float32 at out_ptr,
@@ -1375,8 +1360,7 @@ class Spectrum(_Handle):
         out_stride = self.nfft if out_stride is None else int(out_stride)
         if out_stride < self.nfft:
             raise ValueError(f"out_stride={out_stride} < nfft={self.nfft}")
-        h = self._open()
-        check(self.lib.sdr_spec_process_dev(h, iq_ptr, n, out_ptr, out_stride), "sdr_spec_process_dev")
+        self._do("process_dev", iq_ptr, n, out_ptr, out_stride)
         return rows
 
     def run(self, iq_host) -> np.ndarray:
@@ -1386,8 +1370,7 @@ class Spectrum(_Handle):
         n = iq.size // 2
         rows = self.rows(n)[1]
         out = np.empty((rows, self.nfft), dtype=np.float32)
-        h = self._open()
-        check(self.lib.sdr_spec_run(h, iq.ctypes.data, n, out.ctypes.data, self.nfft), "sdr_spec_run")
+        self._do("run", iq.ctypes.data, n, out.ctypes.data, self.nfft)
         return out
 
 
@@ -1475,15 +1458,8 @@ class RowSpectrum(Spectrum):
         """The nfft / 2 + 1 bin centres, 0 .. fs / 2: k fs / nfft."""
         return np.arange(self.nbins) * (self.fs / self.nfft)
 
-    def _open(self):
-        if self.handle is None:
-            self.ctx = self._ctx if self._ctx is not None else _lib.get_context()
-            self.lib = self.ctx.lib
-            h = ctypes.c_void_p()
-            check(self.lib.sdr_rspec_create(self.ctx.handle, self.nrows, self.nfft, f64p(self.window), self.hop, self.navg,
-                                            ctypes.byref(h)), "sdr_rspec_create")
-            self.handle = h
-        return self.handle
+    def _create_args(self):
+        return self.nrows, self.nfft, f64p(self.window), self.hop, self.navg
 
     def process_dev(self, x_ptr: int, n: int, in_stride: int, out_ptr: int, out_stride=None) -> int:
         """n samples per row at device pointer x_ptr, rows in_stride floats apart -> per input row
@@ -1497,8 +1473,7 @@ class RowSpectrum(Spectrum):
             raise ValueError(f"in_stride={in_stride} < n={n}")
         if out_stride < self.nbins:
             raise ValueError(f"out_stride={out_stride} < nfft/2+1={self.nbins}")
-        h = self._open()
-        check(self.lib.sdr_rspec_process_dev(h, x_ptr, n, in_stride, out_ptr, out_stride), "sdr_rspec_process_dev")
+        self._do("process_dev", x_ptr, n, in_stride, out_ptr, out_stride)
         return rows
 
     def process_rx(self, receiver: "Receiver", out_ptr: int, name: str = "demod", out_stride=None) -> int:
@@ -1518,8 +1493,7 @@ class RowSpectrum(Spectrum):
         n = x.shape[1]
         rows = self.rows(n)[1]
         out = np.empty((self.nrows, rows, self.nbins), dtype=np.float32)
-        h = self._open()
-        check(self.lib.sdr_rspec_run(h, x.ctypes.data, n, n, out.ctypes.data, self.nbins), "sdr_rspec_run")
+        self._do("run", x.ctypes.data, n, n, out.ctypes.data, self.nbins)
         return out
 
 
@@ -1579,7 +1553,7 @@ class _RmeterRecordC(ctypes.Structure):                          # include/sdr.h
                 for k in rowmeter.FIELDS]
 
 
-class RowMeter(_Handle):
+class RowMeter(_Timed, _LazyHandle):
     """The modulation meter of `nstreams` rows of real float32 samples on the GPU (sdr_rmeter,
     csrc/rmeter.hip) -- a Receiver's "demod" or audio rows, read where the receiver left them.  Per
     stream and carried from call to call: the call's and the totals' finite / non-finite / over-limit
@@ -1596,20 +1570,14 @@ class RowMeter(_Handle):
     CHUNK, SEG = _lib.SDR_RMETER_CHUNK, _lib.SDR_RMETER_SEG      # a window from SEG samples on is cut into chunks of at most CHUNK
     MAX_N = rowmeter.MAX_N
     _prefix = "sdr_rmeter"
+    _STAGES = ("reduce", "fold")                                 # stage_ms: the last call's two launches
 
     def __init__(self, nstreams: int, window: int, nbins: int = 128, scale: float = 1.0, limit: float = np.inf, ctx=None):
         self.nstreams, self.window, self.nbins, self.scale, self.limit = rowmeter.check_params(nstreams, window, nbins, scale, limit)
         self._ctx = ctx
 
-    def _open(self):
-        if self.handle is None:
-            self.ctx = self._ctx if self._ctx is not None else _lib.get_context()
-            self.lib = self.ctx.lib
-            h = ctypes.c_void_p()
-            prm = _RmeterParamsC(self.window, self.nbins, float(self.scale), float(self.limit))
-            check(self.lib.sdr_rmeter_create(self.ctx.handle, self.nstreams, ctypes.byref(prm), ctypes.byref(h)), "sdr_rmeter_create")
-            self.handle = h
-        return self.handle
+    def _create_args(self):
+        return self.nstreams, ctypes.byref(_RmeterParamsC(self.window, self.nbins, float(self.scale), float(self.limit)))
 
     def process_dev(self, ptr: int, stride: int, n: int):
         """n samples per row at device pointer ptr, rows stride floats apart (the floats between rows
@@ -1623,8 +1591,7 @@ class RowMeter(_Handle):
             raise ValueError(f"stride={stride} < n={n}")
         if ptr % 4:
             raise ValueError("ptr must be aligned to 4 B")
-        h = self._open()
-        check(self.lib.sdr_rmeter_process_dev(h, ptr, stride, n), "sdr_rmeter_process_dev")
+        self._do("process_dev", ptr, stride, n)
 
     def process_rx(self, receiver: "Receiver", name: str = "demod"):
         """The receiver's latest rows of output `name`, read in place (looked up at every call: a
@@ -1637,57 +1604,38 @@ class RowMeter(_Handle):
     def run(self, rows_host):
         """(nstreams, n) real samples from the host; synchronous (sdr_rmeter_run)."""
         x = np.ascontiguousarray(rowmeter.as_rows(rows_host, self.nstreams))
-        h = self._open()
-        check(self.lib.sdr_rmeter_run(h, x.ctypes.data, x.shape[1], x.shape[1]), "sdr_rmeter_run")
+        self._do("run", x.ctypes.data, x.shape[1], x.shape[1])
 
     def records(self) -> "rowmeter.RowMeterRecord":
         """The state after the latest call, an array entry per stream (sdr_rmeter_records; synchronises)."""
         raw = (_RmeterRecordC * self.nstreams)()
-        h = self._open()
-        check(self.lib.sdr_rmeter_records(h, ctypes.byref(raw)), "sdr_rmeter_records")
+        self._do("records", ctypes.byref(raw))
         return rowmeter.RowMeterRecord(*(np.array([getattr(r, k) for r in raw], dtype=rowmeter.field_dtype(k)) for k in rowmeter.FIELDS))
 
     def hist(self) -> np.ndarray:
         """uint64[nstreams, nbins] (sdr_rmeter_hist; synchronises)."""
         out = np.empty((self.nstreams, self.nbins), dtype=np.uint64)
-        h = self._open()
-        check(self.lib.sdr_rmeter_hist(h, out.ctypes.data), "sdr_rmeter_hist")
+        self._do("hist", out.ctypes.data)
         return out
 
     def windows(self) -> np.ndarray:
         """float32[nstreams, windows, 2]: (min, max) of the windows the latest call completed, in
         order; (+inf, -inf) for one without a finite sample (sdr_rmeter_windows; synchronises)."""
-        h = self._open()
         counts = np.zeros(self.nstreams, dtype=np.int64)
-        check(self.lib.sdr_rmeter_windows(h, None, 0, counts.ctypes.data), "sdr_rmeter_windows")
+        self._do("windows", None, 0, counts.ctypes.data)
         out = np.empty((self.nstreams, int(counts[0]), 2), dtype=np.float32)
         if out.size:
-            check(self.lib.sdr_rmeter_windows(h, out.ctypes.data, out.shape[1], None), "sdr_rmeter_windows")
+            self._do("windows", out.ctypes.data, out.shape[1], None)
         return out
 
     def state_ptr(self):
         """(record pointer, histogram pointer): the device arrays of struct sdr_rmeter_record [nstreams]
         and uint64 [nstreams][nbins] (sdr_rmeter_state_dev)."""
-        p, q = ctypes.c_void_p(), ctypes.c_void_p()
-        h = self._open()
-        check(self.lib.sdr_rmeter_state_dev(h, ctypes.byref(p), ctypes.byref(q)), "sdr_rmeter_state_dev")
-        return p.value, q.value
+        return self._ptr_out("state_dev", 2)
 
     def reset(self):
         """Zero the records, the histogram and the stream position (async)."""
-        h = self._open()
-        check(self.lib.sdr_rmeter_reset(h), "sdr_rmeter_reset")
-
-    def set_timing(self, on: bool = True):
-        """Record HIP events around the two launches of each call (stage_ms)."""
-        h = self._open()
-        check(self.lib.sdr_rmeter_set_timing(h, int(bool(on))), "sdr_rmeter_set_timing")
-
-    def stage_ms(self) -> dict:
-        """GPU time of the last call's launches (set_timing(True) first): reduce, fold."""
-        ms = np.zeros(2, dtype=np.float32)
-        check(self.lib.sdr_rmeter_stage_ms(self.handle, ms.ctypes.data_as(_lib._fp)), "sdr_rmeter_stage_ms")
-        return dict(zip(("reduce", "fold"), (float(v) for v in ms)))
+        self._do("reset")
 
 
 class _BlendParamsC(ctypes.Structure):                           # include/sdr.h sdr_blend_params
@@ -1749,7 +1697,7 @@ def _check_mpx_bins(nbins: int, fs: float):
 BlendState = collections.namedtuple("BlendState", "pilot_snr_db rds_snr_db noise_floor stereo_gain mute_gain")
 
 
-class BlendControl(_Handle):
+class BlendControl(_LazyHandle):
     """Stereo blend and noise mute gains of `nstreams` streams from their multiplex spectra, on the
     GPU (sdr_blend, csrc/blend.hip): update_dev reads one RowSpectrum row (navg=0) per stream,
     computes mpx_quality's pilot and RDS ratios and noise floor in f64, and moves each stream's
@@ -1775,15 +1723,8 @@ class BlendControl(_Handle):
         self.nstreams, self.params = nstreams, _blend_params(params)
         self._ctx = ctx
 
-    def _open(self):
-        if self.handle is None:
-            self.ctx = self._ctx if self._ctx is not None else _lib.get_context()
-            self.lib = self.ctx.lib
-            h = ctypes.c_void_p()
-            check(self.lib.sdr_blend_create(self.ctx.handle, self.nstreams, ctypes.byref(self.params._c()), ctypes.byref(h)),
-                  "sdr_blend_create")
-            self.handle = h
-        return self.handle
+    def _create_args(self):
+        return self.nstreams, ctypes.byref(self.params._c())
 
     def update_dev(self, power_ptr: int, nbins: int, stride: int, fs: float):
         """One update from nstreams rows of nbins float32 power bins at device pointer power_ptr,
@@ -1794,15 +1735,13 @@ class BlendControl(_Handle):
         _check_mpx_bins(nbins, fs)
         if stride < nbins:
             raise ValueError(f"stride={stride} < nbins={nbins}")
-        h = self._open()
-        check(self.lib.sdr_blend_update_dev(h, power_ptr, nbins, stride, fs), "sdr_blend_update_dev")
+        self._do("update_dev", power_ptr, nbins, stride, fs)
 
     def raw_state(self) -> np.ndarray:
         """(nstreams, 8) float64: pilot_db, rds_db, noise_floor, g_prev, g, m_prev, m, n_updates
         (sdr_blend_state; synchronises)."""
         out = np.empty((self.nstreams, self.NSTATE))
-        h = self._open()
-        check(self.lib.sdr_blend_state(h, f64p(out)), "sdr_blend_state")
+        self._do("state", f64p(out))
         return out
 
     def state(self) -> BlendState:
@@ -1812,15 +1751,11 @@ class BlendControl(_Handle):
     @property
     def gains_ptr(self) -> int:
         """The device array (nstreams, 4) float64 {g_prev, g, m_prev, m} (sdr_blend_gains_dev)."""
-        p = ctypes.c_void_p()
-        h = self._open()
-        check(self.lib.sdr_blend_gains_dev(h, ctypes.byref(p)), "sdr_blend_gains_dev")
-        return p.value
+        return self._ptr_out("gains_dev")
 
     def reset(self):
         """Back to the state after creation (async)."""
-        h = self._open()
-        check(self.lib.sdr_blend_reset(h), "sdr_blend_reset")
+        self._do("reset")
 
 
 def _blend_state(raw) -> BlendState:

@@ -20,12 +20,6 @@ namespace {
 
 constexpr int MAXG = SDR_BLEND_MAX_GUARD;
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);   // the same order in every lane
-  return v;
-}
-
 // sum of row[b0 .. b1) in f64: lane-strided partial sums, then the butterfly
 __device__ __forceinline__ double band_sum(const float* __restrict__ row, int b0, int b1, int lane) {
   double acc = 0.0;

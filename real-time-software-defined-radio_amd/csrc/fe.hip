@@ -185,7 +185,7 @@ __device__ __forceinline__ float fe_epilogue(const FeParams& p, int s, int64_t M
       if (mf + r == M - 1) p.last_phi[s] = phi[r];
   }
   if (p.wraps != nullptr) {
-    wsum = wave_sum_i(wsum);
+    wsum = wave_sum<int>(wsum);
     if (lane == 0 && wsum != 0) atomicAdd(p.wraps + s, wsum);
   }
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(phi[R - 1]), 63));
@@ -801,7 +801,7 @@ __global__ __launch_bounds__(64) void fe_ring_kernel(FeParams p, TapsF32 taps, R
 
     // ---- advance ----
     if ((s1 != s || u + 1 == U) && p.wraps != nullptr) {
-      const int w = wave_sum_i(wacc);
+      const int w = wave_sum<int>(wacc);
       if (w != 0) {
         if (lane == 0) atomicAdd(p.wraps + s, w);
         issued += 1;
@@ -1128,7 +1128,7 @@ void fe_slot_kernel(FeParams p, TapsF32 taps, SlotArgs a) {
     }
 
     if ((s1 != s || lastu) && p.wraps != nullptr) {
-      const int w = wave_sum_i(wacc);
+      const int w = wave_sum<int>(wacc);
       if (lane == 0 && w != 0) atomicAdd(p.wraps + s, w);
       wacc = 0;
     }
@@ -1371,7 +1371,7 @@ __global__ __launch_bounds__(256) void demod_kernel(const float* I, const float*
     if (k == n - 1 && last_phi != nullptr) last_phi[s] = phi;
   }
   if (wraps != nullptr) {
-    wk = wave_sum_i(wk);
+    wk = wave_sum<int>(wk);
     if ((threadIdx.x & 63) == 0 && wk != 0) atomicAdd(wraps + s, wk);
   }
 }

@@ -526,7 +526,7 @@ __device__ __forceinline__ float output_phase(const unsigned char* iq_s, int64_t
 #pragma unroll
   for (int ch = 0; ch < 2; ++ch)
 #pragma unroll
-    for (int dg = 0; dg < 3; ++dg) acc[ch][dg] = wave_sum_i(acc[ch][dg]);
+    for (int dg = 0; dg < 3; ++dg) acc[ch][dg] = wave_sum<int>(acc[ch][dg]);
   const float yi = fmaf((float)acc[0][2], 65536.f, (float)(acc[0][1] * 256 + acc[0][0]));   // combine_digits
   const float yq = fmaf((float)acc[1][2], 65536.f, (float)(acc[1][1] * 256 + acc[1][0]));
   return fast_atan2f_x2(f2v{yq, yq}, f2v{yi, yi}).x;
@@ -744,7 +744,7 @@ __global__ __launch_bounds__(64) void fe_mfma_demod_kernel(MfmaDemod p) {
     // the stream's wrap count leaves with its last tile of this run
     const bool wr = keep && (!more || s_nx != s) && p.wraps != nullptr;
     if (wr) {
-      const int w = wave_sum_i(wsum);
+      const int w = wave_sum<int>(wsum);
       if (lane == 0 && w != 0) atomicAdd(p.wraps + s, w);
       wsum = 0;
     }

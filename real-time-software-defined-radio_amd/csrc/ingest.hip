@@ -4,21 +4,20 @@
 // meter: samples on a rail, the peak, the sum of squares.  The reference has no such stage; the
 // definition is rtsdr.ingest_model (capture.py).  Two launches, nothing returns to the host:
 //
-//   ingest_kernel<FMT, SWAP, METER>  workgroup b takes the samples [b chunk, (b + 1) chunk), as
-//       iqc.hip's moments pass does: 16-B loads from the first 16-B boundary of its chunk on (eight
-//       8-bit samples, four s16 samples or two f32 samples a lane), the samples before it and after
-//       the last whole vector one by one.  Each input byte is read once.  The meter is taken on the
-//       lane's own vector; the integer formats then pass the vector through a 1-KiB LDS tile per
+//   ingest_kernel<FMT, SWAP, METER>  workgroup b takes the samples [b chunk, (b + 1) chunk) by
+//       sdr_chunk.h's range pass (eight 8-bit samples, four s16 samples or two f32 samples a 16-B
+//       load).  Each input byte is read once.  The meter is taken on the lane's own vector; at the
+//       end of a round of loads the integer formats pass their vectors through a 1-KiB LDS tile per
 //       wave and load, so that lane l of store j holds the tile's sample pair 64 j + l: every wave
 //       store covers 1 KiB of contiguous output (one 16-B store a lane, or two 8-B halves where
 //       out's 16-B phase differs from the pairs').  The tile is the wave's own: no workgroup
 //       barrier in the loop.  f32 is two samples a lane and needs no tile; it moves as bits, so
 //       NaN payloads pass, and every lane loads before it stores, so it runs in place.
 //       out = f32(code) 2^-(bits - 1): the conversion and the power-of-two product are exact.
-//       METER: lane partials -> xor butterfly -> the four waves through LDS in wave order -> one
-//       record (clipped, nonfinite, peak, sumsq) per workgroup.  No atomics.
-//   ingest_fold_kernel  one wave: the records lane-strided in ascending order, the butterfly, then
-//       lane 0 stores the call's meter and adds to the carried totals.
+//       METER: the lane partials become one record (clipped, nonfinite, peak, sumsq) per workgroup
+//       by sdr_chunk.h's block record.  No atomics.
+//   ingest_fold_kernel  one wave: sdr_chunk.h's fold of the records, then lane 0 stores the call's
+//       meter and adds to the carried totals.
 //
 // With the meter off the stage is the first launch alone.
 #include <hip/hip_runtime.h>
@@ -39,10 +38,12 @@ constexpr int ING_WAVES = ING_THREADS / 64;
 constexpr int ING_MAX_WG = 2048;                  // partial records per call
 constexpr int ING_U = 4;                          // loads in flight per lane and round
 constexpr int ING_NREC = 4;                       // clipped, nonfinite, peak, sumsq
+constexpr int ING_FOLD_U = 8;                     // the fold's record loads in flight per lane
 static_assert(SDR_INGEST_CHUNK % 8 == 0, "whole 16-B vectors of every type");
-// The 8-bit lane partial of the sum of squares is 32 bits wide and goes to 64 bits after every
-// round: ING_U vectors of 8 samples, each sample at most 2 x 128^2.
-static_assert((uint64_t)ING_U * 8 * 2 * 128 * 128 <= 0xffffffffull, "the 32-bit lane partial cannot overflow within a round");
+// The 8-bit lane partial of the sum of squares is 32 bits wide: a lane's samples of the largest
+// chunk, each at most 2 x 128^2.
+static_assert((uint64_t)lane_share(max_chunk(SDR_INGEST_CHUNK, ING_MAX_WG), 8, ING_THREADS) * 2 * 128 * 128 <= 0xffffffffull,
+              "the 32-bit lane partial cannot overflow within a chunk");
 // One s16 sample adds up to 2 x 32768^2 = 2^31: it fits 32 bits, two do not.  The s16 lane partial
 // is 64 bits wide from the first sample on; a chunk of at most 2^31 samples stays below 2^62.
 static_assert((uint64_t)2 * 32768 * 32768 <= 0xffffffffull, "one s16 sample's squares fit the 32-bit term");
@@ -53,23 +54,17 @@ constexpr int es_of(int fmt) { return fmt == SDR_IQ_F32 ? 8 : fmt == SDR_IQ_S16 
 // the lane's share of the meter, integer formats: exact
 template <bool WIDE>
 struct MeterInt {
-  uint32_t clipped = 0, nonfinite = 0, peak = 0, s = 0;
-  uint64_t S = 0;
+  uint32_t clipped = 0, nonfinite = 0, peak = 0;
+  std::conditional_t<WIDE, uint64_t, uint32_t> sq = 0;
   int hi, lo;                                     // the rails: 2^(bits - 1) - 1 and -2^(bits - 1)
   __device__ __forceinline__ void add(int ci, int cq) {
     const int mx = ci > cq ? ci : cq, mn = ci < cq ? ci : cq;
     clipped += (mx >= hi || mn <= lo) ? 1u : 0u;
     const uint32_t a = (uint32_t)(mx > -mn ? mx : -mn);            // max(|ci|, |cq|); -lo counts with its magnitude
     peak = a > peak ? a : peak;
-    const uint32_t q = (uint32_t)(ci * ci) + (uint32_t)(cq * cq);
-    if constexpr (WIDE) S += q;
-    else s += q;
+    sq += (uint32_t)(ci * ci) + (uint32_t)(cq * cq);
   }
-  __device__ __forceinline__ void flush() {
-    S += s;
-    s = 0;
-  }
-  __device__ __forceinline__ uint64_t sumsq_bits() const { return S + s; }
+  __device__ __forceinline__ unsigned long long sumsq() const { return sq; }
 };
 
 // f32: a sample with a non-finite I or Q counts there and nowhere else; |x| of a finite float
@@ -86,8 +81,22 @@ struct MeterF32 {
     const double di = fin ? (double)__builtin_bit_cast(float, bi) : 0.0, dq = fin ? (double)__builtin_bit_cast(float, bq) : 0.0;
     S = __builtin_fma(dq, dq, __builtin_fma(di, di, S));
   }
-  __device__ __forceinline__ void flush() {}
-  __device__ __forceinline__ uint64_t sumsq_bits() const { return __builtin_bit_cast(uint64_t, S); }
+  __device__ __forceinline__ double sumsq() const { return S; }
+};
+
+// the meter's record: the sum of squares -- u64, exact, or f64 --, the counts (a call has fewer than
+// 2^31 samples) and the peak (an integer maximum); value k of workgroup b is the 8-byte word
+// part[k ING_MAX_WG + b], so the fold's lane-strided loads are contiguous
+template <class ST>
+struct IngRec {
+  ST sumsq;
+  uint32_t clipped, nonfinite, peak, pad;
+  __device__ __forceinline__ void combine(const IngRec& o) {
+    clipped += o.clipped;
+    nonfinite += o.nonfinite;
+    peak = o.peak > peak ? o.peak : peak;
+    sumsq += o.sumsq;
+  }
 };
 
 template <int FMT>
@@ -131,16 +140,6 @@ __device__ __forceinline__ f2 out_pair(int ci, int cq, float scale) {
   return SWAP ? f2{fq, fi} : f2{fi, fq};
 }
 
-// two samples = 16 B of output, contiguous across the wave
-__device__ __forceinline__ void store_pair(float* q, bool out16, const f4 v) {
-  if (out16) {
-    *reinterpret_cast<f4*>(q) = v;
-  } else {
-    *reinterpret_cast<f2*>(q) = f2{v.x, v.y};
-    *reinterpret_cast<f2*>(q + 2) = f2{v.z, v.w};
-  }
-}
-
 // One sample taken alone: loaded, metered, stored at out[2 s].  raw and out are aligned to one
 // sample, so the accesses are whole.
 template <int FMT, bool SWAP, bool METER>
@@ -164,45 +163,6 @@ __device__ __forceinline__ void ingest_one(const char* q, float* o, float scale,
   }
 }
 
-// lane partials -> one record per workgroup, in a fixed order; value k of workgroup b is
-// part[k ING_MAX_WG + b], so the fold's lane-strided loads are contiguous
-template <int FMT>
-__device__ __forceinline__ void block_record(const Meter<FMT>& m, unsigned long long* __restrict__ part) {
-  using ST = std::conditional_t<is_f32(FMT), double, unsigned long long>;
-  __shared__ unsigned long long wp[ING_WAVES][ING_NREC];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const uint32_t clipped = wave_sum64(m.clipped), nonfinite = wave_sum64(m.nonfinite);   // a chunk has at most 2^20 samples
-  uint32_t peak = m.peak;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t other = __shfl_xor(peak, o, 64);
-    peak = other > peak ? other : peak;
-  }
-  const ST sumsq = wave_sum64(__builtin_bit_cast(ST, m.sumsq_bits()));
-  if (lane == 0) {
-    wp[w][0] = clipped;
-    wp[w][1] = nonfinite;
-    wp[w][2] = peak;
-    wp[w][3] = __builtin_bit_cast(unsigned long long, sumsq);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long c = wp[0][0], nf = wp[0][1], pk = wp[0][2];
-    ST s = __builtin_bit_cast(ST, wp[0][3]);
-#pragma unroll
-    for (int j = 1; j < ING_WAVES; ++j) {
-      c += wp[j][0];
-      nf += wp[j][1];
-      pk = wp[j][2] > pk ? wp[j][2] : pk;
-      s += __builtin_bit_cast(ST, wp[j][3]);
-    }
-    part[0 * ING_MAX_WG + blockIdx.x] = c;
-    part[1 * ING_MAX_WG + blockIdx.x] = nf;
-    part[2 * ING_MAX_WG + blockIdx.x] = pk;
-    part[3 * ING_MAX_WG + blockIdx.x] = __builtin_bit_cast(unsigned long long, s);
-  }
-}
-
 // raw and out may be the same f32 block: neither is __restrict__
 template <int FMT, bool SWAP, bool METER>
 __global__ __launch_bounds__(ING_THREADS) void ingest_kernel(const void* raw, int64_t n, int64_t chunk, float scale, int hi, int lo,
@@ -210,9 +170,7 @@ __global__ __launch_bounds__(ING_THREADS) void ingest_kernel(const void* raw, in
   constexpr int ES = es_of(FMT);
   constexpr int NST = 16 / ES / 2;                                  // sample pairs = 16-B stores of a 16-B load
   const Chunk<ES> c(raw, n, chunk);
-  const u4* v = c.vec();
-  const int64_t s0 = (int64_t)blockIdx.x * chunk;
-  float* oc = out + 2 * s0;                                         // the chunk's output
+  float* oc = out + 2 * (int64_t)blockIdx.x * chunk;                // the chunk's output
   float* ov = oc + 2 * c.head;                                      // and that of its vectors
   const bool out16 = ((uintptr_t)ov & 15) == 0;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -221,72 +179,66 @@ __global__ __launch_bounds__(ING_THREADS) void ingest_kernel(const void* raw, in
     m.hi = hi;
     m.lo = lo;
   }
-  for (int64_t i0 = 0; i0 < c.nv; i0 += ING_THREADS * ING_U) {
-    u4 x[ING_U];
-    bool in[ING_U];
-#pragma unroll
-    for (int u = 0; u < ING_U; ++u) {
-      const int64_t i = i0 + ING_THREADS * u + threadIdx.x;
-      in[u] = i < c.nv;
-      x[u] = in[u] ? __builtin_nontemporal_load(v + i) : u4{0u, 0u, 0u, 0u};
-    }
-    if constexpr (METER) {
-#pragma unroll
-      for (int u = 0; u < ING_U; ++u)
-        if (in[u]) meter_vec<FMT>(m, x[u]);
-      m.flush();
-    }
-    if constexpr (is_f32(FMT)) {
-#pragma unroll
-      for (int u = 0; u < ING_U; ++u)
-        if (in[u]) {
-          const u4 y = SWAP ? u4{x[u].y, x[u].x, x[u].w, x[u].z} : x[u];
-          store_pair(ov + 4 * (i0 + ING_THREADS * u + threadIdx.x), out16, __builtin_bit_cast(f4, y));
+  scan_range<ES, ING_THREADS, ING_U>(
+      c.p, c, threadIdx.x,
+      [&](const u4 x, int64_t i) {
+        if constexpr (METER) meter_vec<FMT>(m, x);
+        if constexpr (is_f32(FMT)) {
+          const u4 y = SWAP ? u4{x.y, x.x, x.w, x.z} : x;
+          store_pair(ov + 4 * i, out16, __builtin_bit_cast(f4, y));
         }
-    } else {
-      // the wave's own tiles: lane l's vector at 16 l, pair p of the tile read back at 16 p / NST
-      using PT = std::conditional_t<NST == 4, uint32_t, uint2>;
-      __shared__ u4 tile[ING_WAVES][ING_U][64];
+      },
+      [&](const u4(&x)[ING_U], int64_t i0) {
+        if constexpr (!is_f32(FMT)) {
+          // the wave's own tiles: lane l's vector at 16 l, pair p of the tile read back at 16 p / NST
+          using PT = std::conditional_t<NST == 4, uint32_t, uint2>;
+          __shared__ u4 tile[ING_WAVES][ING_U][64];
 #pragma unroll
-      for (int u = 0; u < ING_U; ++u) tile[w][u][lane] = x[u];
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+          for (int u = 0; u < ING_U; ++u) tile[w][u][lane] = x[u];
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          __builtin_amdgcn_wave_barrier();
 #pragma unroll
-      for (int u = 0; u < ING_U; ++u) {
-        const int64_t vb = i0 + ING_THREADS * u + 64 * w;             // the wave's first vector of this load
-        const PT* t = reinterpret_cast<const PT*>(&tile[w][u][0]);
+          for (int u = 0; u < ING_U; ++u) {
+            const int64_t vb = i0 + ING_THREADS * u + 64 * w;             // the wave's first vector of this load
+            const PT* t = reinterpret_cast<const PT*>(&tile[w][u][0]);
 #pragma unroll
-        for (int j = 0; j < NST; ++j) {
-          const int p = 64 * j + lane;
-          if (vb + p / NST < c.nv) {
-            f2 a, b;
-            if constexpr (NST == 4) {
-              int k[4];
-              codes8<FMT>(t[p], k);
-              a = out_pair<SWAP>(k[0], k[1], scale);
-              b = out_pair<SWAP>(k[2], k[3], scale);
-            } else {
-              const uint2 d = t[p];
-              int ci, cq;
-              codes16(d.x, ci, cq);
-              a = out_pair<SWAP>(ci, cq, scale);
-              codes16(d.y, ci, cq);
-              b = out_pair<SWAP>(ci, cq, scale);
+            for (int j = 0; j < NST; ++j) {
+              const int p = 64 * j + lane;
+              if (vb + p / NST < c.nv) {
+                f2 a, b;
+                if constexpr (NST == 4) {
+                  int k[4];
+                  codes8<FMT>(t[p], k);
+                  a = out_pair<SWAP>(k[0], k[1], scale);
+                  b = out_pair<SWAP>(k[2], k[3], scale);
+                } else {
+                  const uint2 d = t[p];
+                  int ci, cq;
+                  codes16(d.x, ci, cq);
+                  a = out_pair<SWAP>(ci, cq, scale);
+                  codes16(d.y, ci, cq);
+                  b = out_pair<SWAP>(ci, cq, scale);
+                }
+                store_pair(ov + 4 * (vb * NST + p), out16, f4{a.x, a.y, b.x, b.y});
+              }
             }
-            store_pair(ov + 4 * (vb * NST + p), out16, f4{a.x, a.y, b.x, b.y});
           }
+          // the next round's tile writes come after this round's reads
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          __builtin_amdgcn_wave_barrier();
         }
-      }
-      // the next round's tile writes come after this round's reads
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-    }
+      },
+      // the single samples: no vector holds them, so no other thread reads or writes them
+      [&](const char* q) { ingest_one<FMT, SWAP, METER>(q, oc + 2 * ((q - c.p) / ES), scale, m); });
+  if constexpr (METER) {
+    using ST = decltype(m.sumsq());
+    block_record<ING_WAVES>(IngRec<ST>{m.sumsq(), m.clipped, m.nonfinite, m.peak, 0}, [&](const IngRec<ST>& r) {
+      part[0 * ING_MAX_WG + blockIdx.x] = r.clipped;
+      part[1 * ING_MAX_WG + blockIdx.x] = r.nonfinite;
+      part[2 * ING_MAX_WG + blockIdx.x] = r.peak;
+      part[3 * ING_MAX_WG + blockIdx.x] = __builtin_bit_cast(unsigned long long, r.sumsq);
+    });
   }
-  // the single samples: no vector holds them, so no other thread reads or writes them
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-    if (const char* q = c.single(k)) ingest_one<FMT, SWAP, METER>(q, oc + 2 * ((q - c.p) / ES), scale, m);
-  if constexpr (METER) block_record<FMT>(m, part);
 }
 
 struct IngFold {
@@ -296,30 +248,25 @@ struct IngFold {
   int nwg, f32, bits;
 };
 
+template <class ST>
+__device__ __forceinline__ IngRec<ST> fold_meter(const unsigned long long* __restrict__ p, int nwg, int lane) {
+  return fold_records<ING_FOLD_U>(nwg, lane, IngRec<ST>{ST(0), 0, 0, 0, 0}, [&](int b) {
+    return IngRec<ST>{__builtin_bit_cast(ST, p[3 * ING_MAX_WG + b]), (uint32_t)p[0 * ING_MAX_WG + b], (uint32_t)p[1 * ING_MAX_WG + b],
+                      (uint32_t)p[2 * ING_MAX_WG + b], 0};
+  });
+}
+
 __global__ __launch_bounds__(64) void ingest_fold_kernel(const IngFold a) {
   const int lane = threadIdx.x;
-  const unsigned long long* __restrict__ p = a.part;
-  unsigned long long clipped = 0, nonfinite = 0, S = 0;
-  uint32_t peak = 0;
+  uint32_t clipped, nonfinite, peak;
+  unsigned long long S = 0;
   double D = 0.0;
-#pragma unroll 8
-  for (int b = lane; b < a.nwg; b += 64) {
-    clipped += p[0 * ING_MAX_WG + b];
-    nonfinite += p[1 * ING_MAX_WG + b];
-    const uint32_t pk = (uint32_t)p[2 * ING_MAX_WG + b];
-    peak = pk > peak ? pk : peak;
-    const unsigned long long s = p[3 * ING_MAX_WG + b];
-    if (a.f32) D += __builtin_bit_cast(double, s);
-    else S += s;
-  }
-  clipped = wave_sum64(clipped);
-  nonfinite = wave_sum64(nonfinite);
-  S = wave_sum64(S);
-  D = wave_sum64(D);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t other = __shfl_xor(peak, o, 64);
-    peak = other > peak ? other : peak;
+  if (a.f32) {
+    const IngRec<double> r = fold_meter<double>(a.part, a.nwg, lane);
+    clipped = r.clipped; nonfinite = r.nonfinite; peak = r.peak; D = r.sumsq;
+  } else {
+    const IngRec<unsigned long long> r = fold_meter<unsigned long long>(a.part, a.nwg, lane);
+    clipped = r.clipped; nonfinite = r.nonfinite; peak = r.peak; S = r.sumsq;
   }
   if (lane != 0) return;
   sdr_ingest_meter* __restrict__ m = a.m;
@@ -349,7 +296,8 @@ constexpr int container_bits(int dtype) { return dtype == SDR_IQ_F32 ? 32 : dtyp
 struct sdr_ingest {
   sdr_ctx* ctx = nullptr;
   int dtype = 0, bits = 0, swap = 0, meter = 1;
-  sdr_ingest_meter* st = nullptr;      // the meter
+  DevMem mem;
+  sdr_ingest_meter* st = nullptr;      // the meter: all-zero bits (0 and 0.0) after a reset
   unsigned long long* part = nullptr;  // [ING_NREC][ING_MAX_WG] partial records
 };
 
@@ -374,13 +322,9 @@ int sdr_ingest_create(sdr_ctx* c, int iq_dtype, const sdr_ingest_params* params,
   d->bits = bits;
   d->swap = params != nullptr ? (params->swap != 0) : 0;
   d->meter = params != nullptr ? (params->meter != 0) : 1;
-  hipError_t e = hipMalloc(&d->st, sizeof(sdr_ingest_meter));
-  if (e == hipSuccess) e = hipMalloc(&d->part, (size_t)ING_MAX_WG * ING_NREC * 8);
-  if (e != hipSuccess) {
-    sdr_ingest_destroy(d);
-    return create_failed(e, "sdr_ingest_create");
-  }
-  const int rc = sdr_ingest_reset(d);
+  d->mem.get(&d->st, 1, true);
+  d->mem.get(&d->part, (size_t)ING_MAX_WG * ING_NREC);
+  const int rc = d->mem.err != hipSuccess ? create_failed(d->mem.err, "sdr_ingest_create") : sdr_ingest_reset(d);
   if (rc != SDR_OK) {
     sdr_ingest_destroy(d);
     return rc;
@@ -392,37 +336,20 @@ int sdr_ingest_create(sdr_ctx* c, int iq_dtype, const sdr_ingest_params* params,
 void sdr_ingest_destroy(sdr_ingest* d) {
   if (d == nullptr) return;
   if (d->ctx != nullptr && set_dev(d->ctx) == SDR_OK) (void)hipStreamSynchronize(d->ctx->stream);
-  (void)hipFree(d->st);
-  (void)hipFree(d->part);
+  d->mem.release();
   delete d;
 }
 
 int sdr_ingest_reset(sdr_ingest* d) {
   if (d == nullptr) return fail(SDR_EINVAL, "sdr_ingest_reset: object is NULL");
   TRY(set_dev(d->ctx));
-  HIP_TRY(hipMemsetAsync(d->st, 0, sizeof(sdr_ingest_meter), d->ctx->stream));   // all-zero bits: 0 and 0.0
+  HIP_TRY(d->mem.zero(d->ctx->stream));
   return SDR_OK;
 }
-
-namespace {
-// the call-time rules, for host and device buffers alike
-int ingest_check_call(const sdr_ingest* d, const void* raw, int64_t n, const float* out, const char* what) {
-  if (d == nullptr) return fail(SDR_EINVAL, "%s: object is NULL", what);
-  if (raw == nullptr || out == nullptr) return fail(SDR_EINVAL, "%s: raw or out is NULL", what);
-  if (n < 1 || n > INT32_MAX) return fail(SDR_EINVAL, "%s: n=%lld outside [1, 2^31 - 1]", what, (long long)n);
-  return SDR_OK;
-}
-}  // namespace
 
 int sdr_ingest_process_dev(sdr_ingest* d, const void* raw, int64_t n, float* out) {
-  TRY(ingest_check_call(d, raw, n, out, "sdr_ingest_process_dev"));
-  const int es = es_of(d->dtype);
-  const bool f32 = d->dtype == SDR_IQ_F32;
-  const uintptr_t a0 = (uintptr_t)raw, a1 = a0 + (uintptr_t)n * es, o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)n * 8;
-  if ((a0 & (es - 1)) != 0 || (o0 & 7) != 0)
-    return fail(SDR_EINVAL, "sdr_ingest_process_dev: raw must be aligned to one complex sample (%d B) and out to 8 B", es);
-  if (a0 < o1 && o0 < a1 && !(f32 && a0 == o0))
-    return fail(SDR_EINVAL, "sdr_ingest_process_dev: raw and out overlap (only out == raw of an f32 object may)");
+  const bool f32 = d != nullptr && d->dtype == SDR_IQ_F32;
+  TRY(capture_check_call("sdr_ingest_process_dev", d, "raw", raw, d != nullptr ? es_of(d->dtype) : 0, n, out, f32));
   sdr_ctx* c = d->ctx;
   TRY(set_dev(c));
   int64_t chunk;
@@ -460,7 +387,7 @@ int sdr_ingest_process_dev(sdr_ingest* d, const void* raw, int64_t n, float* out
 }
 
 int sdr_ingest_run(sdr_ingest* d, const void* raw_host, int64_t n, float* out_host) {
-  TRY(ingest_check_call(d, raw_host, n, out_host, "sdr_ingest_run"));
+  TRY(capture_check_call("sdr_ingest_run", d, "raw", raw_host, 0, n, out_host, false));
   sdr_ctx* c = d->ctx;
   TRY(set_dev(c));
   const size_t es = (size_t)es_of(d->dtype);
@@ -470,10 +397,7 @@ int sdr_ingest_run(sdr_ingest* d, const void* raw_host, int64_t n, float* out_ho
 
 int sdr_ingest_meter_get(sdr_ingest* d, sdr_ingest_meter* host) {
   if (d == nullptr || host == nullptr) return fail(SDR_EINVAL, "sdr_ingest_meter_get: NULL argument");
-  TRY(set_dev(d->ctx));
-  HIP_TRY(hipMemcpyAsync(host, d->st, sizeof(sdr_ingest_meter), hipMemcpyDeviceToHost, d->ctx->stream));
-  HIP_TRY(hipStreamSynchronize(d->ctx->stream));
-  return SDR_OK;
+  return fetch(d->ctx, d->st, 1, host);
 }
 
 int sdr_ingest_meter_dev(sdr_ingest* d, const sdr_ingest_meter** dev) {

@@ -4,14 +4,13 @@
 // (x - 128) / 128) goes through three launches, nothing returns to the host:
 //
 //   iqc_moments_kernel<U8>  the block's five raw sums (I, Q, I^2, Q^2, I Q).  Workgroup b takes the
-//       samples [b chunk, (b + 1) chunk): 16-B loads (two f32 samples or eight u8 samples a lane)
-//       from the first 16-B boundary of its chunk on, the samples before it and after the last
-//       whole vector one by one.  f32: five f64 accumulators a lane (a product of two f32 values
-//       is exact in f64).  u8: integer sums of the raw bytes, four samples' I and four samples' Q
-//       gathered into a dword each (v_perm_b32) and summed by v_dot4_u32_u8, exact; the 32-bit
-//       lane partials go to 64 bits every IQC_U8_FLUSH rounds.  Lane sums -> xor butterfly -> the
-//       four waves through LDS in wave order -> one record per workgroup.  No atomics.
-//   iqc_update_kernel       one wave: the records lane-strided, the butterfly, then lane 0 runs the
+//       samples [b chunk, (b + 1) chunk) by sdr_chunk.h's range pass (two f32 samples or eight u8
+//       samples a 16-B load).  f32: five f64 accumulators a lane (a product of two f32 values is
+//       exact in f64).  u8: integer sums of the raw bytes, four samples' I and four samples' Q
+//       gathered into a dword each (v_perm_b32) and summed by v_dot4_u32_u8, exact; the lane
+//       partials are 32 bits wide, which a lane's share of the largest chunk fits.  The lane sums
+//       become one record per workgroup by sdr_chunk.h's block record.
+//   iqc_update_kernel       one wave: sdr_chunk.h's fold of the records, then lane 0 runs the
 //       rule's steps 2 and 3 in f64 (u8: the integer sums first become the moments of
 //       (x - 128) / 128, exactly) and stores the state and the four coefficients.
 //   iqc_apply_kernel<U8>    I' = f32(I - dI), Q' = f32(c1 (I - dI) + c2 (Q - dQ)) in f64, the
@@ -45,103 +44,80 @@ constexpr int IQC_THREADS = 256;
 constexpr int IQC_WAVES = IQC_THREADS / 64;
 constexpr int IQC_MAX_WG = 2048;                  // partial records per call
 constexpr int IQC_U = 4;                          // loads in flight per lane and round
-constexpr int IQC_U8_FLUSH = 512;                 // rounds between two flushes of the u8 lane partials
-// a round adds IQC_U vectors of 8 samples to a lane's partials, each sample at most 255^2
-static_assert((uint64_t)IQC_U8_FLUSH * IQC_U * 8 * 255 * 255 <= 0xffffffffull, "the 32-bit lane partials cannot overflow between flushes");
+constexpr int IQC_UPD_U = 8;                      // the update's record loads in flight per lane
 static_assert(SDR_IQC_CHUNK % 8 == 0, "whole 16-B vectors of either type");
 static_assert(SDR_IQC_NSTATE == 12, "mI mQ pII pQQ pIQ dI dQ c1 c2 updates skipped holds");
+// the u8 lane partials are 32 bits wide: a lane's samples of the largest chunk, each at most 255^2
+static_assert((uint64_t)lane_share(max_chunk(SDR_IQC_CHUNK, IQC_MAX_WG), 8, IQC_THREADS) * 255 * 255 <= 0xffffffffull,
+              "the 32-bit lane partials cannot overflow within a chunk");
 
 __device__ __forceinline__ float u8f(uint32_t b) { return ((float)b - 128.f) * (1.f / 128.f); }
 
-// lane sums -> one record of five values per workgroup, in a fixed order; value k of workgroup b
-// is part[k IQC_MAX_WG + b], so the update's lane-strided loads are contiguous
+// the five raw sums I, Q, I^2, Q^2, I Q: f64 (f32 samples) or u64 (u8 samples, exact)
 template <class T>
-__device__ __forceinline__ void block_record(T (&a)[5], T* __restrict__ part) {
-  __shared__ T wp[IQC_WAVES][5];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+struct Sum5 {
+  T a[5];
+  __device__ __forceinline__ void combine(const Sum5& o) {
 #pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    a[k] = wave_sum64(a[k]);
-    if (lane == 0) wp[w][k] = a[k];
+    for (int k = 0; k < 5; ++k) a[k] += o.a[k];
   }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    T s = wp[0][threadIdx.x];
-#pragma unroll
-    for (int j = 1; j < IQC_WAVES; ++j) s += wp[j][threadIdx.x];
-    part[threadIdx.x * IQC_MAX_WG + blockIdx.x] = s;
-  }
-}
+};
 
+// value k of workgroup b is part[k IQC_MAX_WG + b], so the update's lane-strided loads are contiguous
 template <bool U8>
 __global__ __launch_bounds__(IQC_THREADS) void iqc_moments_kernel(const void* __restrict__ iq, int64_t n, int64_t chunk,
                                                                   void* __restrict__ part) {
+  using T = std::conditional_t<U8, unsigned long long, double>;
   const Chunk<U8 ? 2 : 8> c(iq, n, chunk);
-  const u4* __restrict__ v = c.vec();
+  Sum5<T> r;
   if constexpr (U8) {
-    unsigned long long S[5] = {0, 0, 0, 0, 0};
-    for (int64_t i0 = threadIdx.x; i0 < c.nv;) {
-      uint32_t s[5] = {0, 0, 0, 0, 0};
-      for (int r = 0; r < IQC_U8_FLUSH && i0 < c.nv; ++r, i0 += IQC_THREADS * IQC_U) {
-        u4 x[IQC_U];
-#pragma unroll
-        for (int u = 0; u < IQC_U; ++u)
-          x[u] = i0 + IQC_THREADS * u < c.nv ? __builtin_nontemporal_load(v + i0 + IQC_THREADS * u) : u4{0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int u = 0; u < IQC_U; ++u)
+    uint32_t s[5] = {0, 0, 0, 0, 0};
+    scan_range<2, IQC_THREADS, IQC_U>(
+        c.p, c, threadIdx.x,
+        [&](const u4 x, int64_t) {
 #pragma unroll
           for (int e = 0; e < 4; e += 2) {                  // two dwords I0 Q0 I1 Q1, I2 Q2 I3 Q3 -> I0 I1 I2 I3, Q0 Q1 Q2 Q3
-            const uint32_t wi = __builtin_amdgcn_perm(x[u][e + 1], x[u][e], 0x06040200u);
-            const uint32_t wq = __builtin_amdgcn_perm(x[u][e + 1], x[u][e], 0x07050301u);
+            const uint32_t wi = __builtin_amdgcn_perm(x[e + 1], x[e], 0x06040200u);
+            const uint32_t wq = __builtin_amdgcn_perm(x[e + 1], x[e], 0x07050301u);
             s[0] = __builtin_amdgcn_udot4(wi, 0x01010101u, s[0], false);
             s[1] = __builtin_amdgcn_udot4(wq, 0x01010101u, s[1], false);
             s[2] = __builtin_amdgcn_udot4(wi, wi, s[2], false);
             s[3] = __builtin_amdgcn_udot4(wq, wq, s[3], false);
             s[4] = __builtin_amdgcn_udot4(wi, wq, s[4], false);
           }
-      }
+        },
+        [&](const char* q) {
+          const uint32_t h = *reinterpret_cast<const uint16_t*>(q), bi = h & 255u, bq = h >> 8;
+          s[0] += bi; s[1] += bq; s[2] += bi * bi; s[3] += bq * bq; s[4] += bi * bq;
+        });
 #pragma unroll
-      for (int k = 0; k < 5; ++k) S[k] += s[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-      if (const char* q = c.single(k)) {
-        const uint32_t h = *reinterpret_cast<const uint16_t*>(q), bi = h & 255u, bq = h >> 8;
-        S[0] += bi; S[1] += bq; S[2] += bi * bi; S[3] += bq * bq; S[4] += bi * bq;
-      }
-    block_record(S, reinterpret_cast<unsigned long long*>(part));
+    for (int k = 0; k < 5; ++k) r.a[k] = s[k];
   } else {
-    double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    double(&a)[5] = r.a;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) a[k] = 0.0;
     auto add = [&](float fi, float fq) {
       const double di = (double)fi, dq = (double)fq;
       a[0] += di; a[1] += dq;
       // (the products are exact in f64: the fused form rounds as a product and a sum do)
       a[2] = __builtin_fma(di, di, a[2]); a[3] = __builtin_fma(dq, dq, a[3]); a[4] = __builtin_fma(di, dq, a[4]);
     };
-    for (int64_t i0 = threadIdx.x; i0 < c.nv; i0 += IQC_THREADS * IQC_U) {
-      u4 x[IQC_U];
-      bool in[IQC_U];
-#pragma unroll
-      for (int u = 0; u < IQC_U; ++u) {
-        in[u] = i0 + IQC_THREADS * u < c.nv;
-        x[u] = in[u] ? __builtin_nontemporal_load(v + i0 + IQC_THREADS * u) : u4{0u, 0u, 0u, 0u};
-      }
-#pragma unroll
-      for (int u = 0; u < IQC_U; ++u)
-        if (in[u]) {
-          const f4 f = __builtin_bit_cast(f4, x[u]);
+    scan_range<8, IQC_THREADS, IQC_U>(
+        c.p, c, threadIdx.x,
+        [&](const u4 x, int64_t) {
+          const f4 f = __builtin_bit_cast(f4, x);
           add(f.x, f.y);
           add(f.z, f.w);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-      if (const char* q = c.single(k)) {
-        const f2 f = *reinterpret_cast<const f2*>(q);
-        add(f.x, f.y);
-      }
-    block_record(a, reinterpret_cast<double*>(part));
+        },
+        [&](const char* q) {
+          const f2 f = *reinterpret_cast<const f2*>(q);
+          add(f.x, f.y);
+        });
   }
+  block_record<IQC_WAVES>(r, [&](const Sum5<T>& w) {
+#pragma unroll
+    for (int k = 0; k < 5; ++k) reinterpret_cast<T*>(part)[k * IQC_MAX_WG + blockIdx.x] = w.a[k];
+  });
 }
 
 struct IqcUpdate {
@@ -152,26 +128,16 @@ struct IqcUpdate {
   double rate;
 };
 
-// the records of the call's workgroups, lane-strided in ascending order, IQC_UPD_U loads of each
-// of the five values in flight; then the butterfly
-constexpr int IQC_UPD_U = 8;
+// the sums of the call's workgroups
 template <class T>
-__device__ __forceinline__ void sum_records(const T* __restrict__ p, int nwg, int lane, T (&s)[5]) {
+__device__ __forceinline__ Sum5<T> sum_records(const void* part, int nwg, int lane) {
+  const T* __restrict__ p = reinterpret_cast<const T*>(part);
+  return fold_records<IQC_UPD_U>(nwg, lane, Sum5<T>{{T(0), T(0), T(0), T(0), T(0)}}, [&](int b) {
+    Sum5<T> x;
 #pragma unroll
-  for (int k = 0; k < 5; ++k) s[k] = T(0);
-  for (int b = lane; b < nwg; b += 64 * IQC_UPD_U) {
-    T x[5][IQC_UPD_U];
-#pragma unroll
-    for (int u = 0; u < IQC_UPD_U; ++u)
-#pragma unroll
-      for (int k = 0; k < 5; ++k) x[k][u] = b + 64 * u < nwg ? p[k * IQC_MAX_WG + b + 64 * u] : T(0);
-#pragma unroll
-    for (int u = 0; u < IQC_UPD_U; ++u)
-#pragma unroll
-      for (int k = 0; k < 5; ++k) s[k] += x[k][u];
-  }
-#pragma unroll
-  for (int k = 0; k < 5; ++k) s[k] = wave_sum64(s[k]);
+    for (int k = 0; k < 5; ++k) x.a[k] = p[k * IQC_MAX_WG + b];
+    return x;
+  });
 }
 
 __global__ __launch_bounds__(64) void iqc_update_kernel(const IqcUpdate a) {
@@ -179,21 +145,19 @@ __global__ __launch_bounds__(64) void iqc_update_kernel(const IqcUpdate a) {
   const double n = (double)a.n;
   double r[5];
   if (a.u8) {
-    unsigned long long S[5];
-    sum_records(reinterpret_cast<const unsigned long long*>(a.part), a.nwg, lane, S);
+    const Sum5<unsigned long long> S = sum_records<unsigned long long>(a.part, a.nwg, lane);
     // sums of (x - 128) / 128 and of their products from the sums of the bytes: integers below 2^53,
     // a division by a power of two, then the one division by n
-    const long long sx = (long long)S[0], sy = (long long)S[1], sxx = (long long)S[2], syy = (long long)S[3], sxy = (long long)S[4];
+    const long long sx = (long long)S.a[0], sy = (long long)S.a[1], sxx = (long long)S.a[2], syy = (long long)S.a[3], sxy = (long long)S.a[4];
     r[0] = (double)(sx - 128 * a.n) / 128.0 / n;
     r[1] = (double)(sy - 128 * a.n) / 128.0 / n;
     r[2] = (double)(sxx - 256 * sx + 16384 * a.n) / 16384.0 / n;
     r[3] = (double)(syy - 256 * sy + 16384 * a.n) / 16384.0 / n;
     r[4] = (double)(sxy - 128 * sx - 128 * sy + 16384 * a.n) / 16384.0 / n;
   } else {
-    double s[5];
-    sum_records(reinterpret_cast<const double*>(a.part), a.nwg, lane, s);
+    const Sum5<double> s = sum_records<double>(a.part, a.nwg, lane);
 #pragma unroll
-    for (int k = 0; k < 5; ++k) r[k] = s[k] / n;
+    for (int k = 0; k < 5; ++k) r[k] = s.a[k] / n;
   }
   if (lane != 0) return;
   double* __restrict__ st = a.st;
@@ -286,13 +250,7 @@ __global__ __launch_bounds__(IQC_THREADS) void iqc_apply_kernel(const void* iq, 
           a = iqc_map((double)f.x, (double)f.y, c);
           b = iqc_map((double)f.z, (double)f.w, c);
         }
-        float* q = o + 4 * (i0 + IQC_THREADS * u);
-        if constexpr (OUT16) {
-          *reinterpret_cast<f4*>(q) = f4{a.x, a.y, b.x, b.y};
-        } else {
-          *reinterpret_cast<f2*>(q) = a;
-          *reinterpret_cast<f2*>(q + 2) = b;
-        }
+        store_pair(o + 4 * (i0 + IQC_THREADS * u), OUT16, f4{a.x, a.y, b.x, b.y});
       }
   }
 }
@@ -303,11 +261,10 @@ struct sdr_iqc {
   sdr_ctx* ctx = nullptr;
   int dtype = 0, dc = 1, balance = 1;
   double rate = 0.125;
+  DevMem mem;
   double* st = nullptr;      // [SDR_IQC_NSTATE]
-  void* part = nullptr;      // [5][IQC_MAX_WG] partial sums
-  bool timing = false;       // events between the launches of each call (sdr_iqc_set_timing)
-  bool timed = false;        // a call with all three launches has been timed
-  hipEvent_t ev[4] = {};
+  char* part = nullptr;      // [5][IQC_MAX_WG] partial sums of 8 bytes
+  StageTimer<3> tm;          // around the launches of a call with an estimate (sdr_iqc_set_timing)
 };
 
 extern "C" {
@@ -327,13 +284,9 @@ int sdr_iqc_create(sdr_ctx* c, int iq_dtype, const sdr_iqc_params* params, sdr_i
   d->rate = rate;
   d->dc = params != nullptr ? (params->dc != 0) : 1;
   d->balance = params != nullptr ? (params->balance != 0) : 1;
-  hipError_t e = hipMalloc(&d->st, SDR_IQC_NSTATE * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&d->part, (size_t)IQC_MAX_WG * 5 * 8);
-  if (e != hipSuccess) {
-    sdr_iqc_destroy(d);
-    return create_failed(e, "sdr_iqc_create");
-  }
-  const int rc = sdr_iqc_reset(d);
+  d->mem.get(&d->st, SDR_IQC_NSTATE);
+  d->mem.get(&d->part, (size_t)IQC_MAX_WG * 5 * 8);
+  const int rc = d->mem.err != hipSuccess ? create_failed(d->mem.err, "sdr_iqc_create") : sdr_iqc_reset(d);
   if (rc != SDR_OK) {
     sdr_iqc_destroy(d);
     return rc;
@@ -345,10 +298,7 @@ int sdr_iqc_create(sdr_ctx* c, int iq_dtype, const sdr_iqc_params* params, sdr_i
 void sdr_iqc_destroy(sdr_iqc* d) {
   if (d == nullptr) return;
   if (d->ctx != nullptr && set_dev(d->ctx) == SDR_OK) (void)hipStreamSynchronize(d->ctx->stream);
-  for (hipEvent_t e : d->ev)
-    if (e) (void)hipEventDestroy(e);
-  (void)hipFree(d->st);
-  (void)hipFree(d->part);
+  d->mem.release();
   delete d;
 }
 
@@ -370,29 +320,14 @@ int sdr_iqc_set(sdr_iqc* d, const double coeff[4]) {
   return SDR_OK;
 }
 
-namespace {
-// the call-time rules, for host and device buffers alike
-int iqc_check_call(const sdr_iqc* d, const void* iq, int64_t n, const float* out, const char* what) {
-  if (d == nullptr) return fail(SDR_EINVAL, "%s: object is NULL", what);
-  if (iq == nullptr || out == nullptr) return fail(SDR_EINVAL, "%s: iq or out is NULL", what);
-  if (n < 1 || n > INT32_MAX) return fail(SDR_EINVAL, "%s: n=%lld outside [1, 2^31 - 1]", what, (long long)n);
-  return SDR_OK;
-}
-}  // namespace
-
 int sdr_iqc_process_dev(sdr_iqc* d, const void* iq, int64_t n, float* out, int estimate) {
-  TRY(iqc_check_call(d, iq, n, out, "sdr_iqc_process_dev"));
-  const bool u8 = d->dtype == SDR_IQ_U8;
-  const int es = u8 ? 2 : 8;
-  const uintptr_t a0 = (uintptr_t)iq, a1 = a0 + (uintptr_t)n * es, o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)n * 8;
-  if ((a0 & (es - 1)) != 0 || (o0 & 7) != 0)
-    return fail(SDR_EINVAL, "sdr_iqc_process_dev: iq must be aligned to one complex sample (%d B) and out to 8 B", es);
-  if (a0 < o1 && o0 < a1 && !(!u8 && a0 == o0))
-    return fail(SDR_EINVAL, "sdr_iqc_process_dev: iq and out overlap (only out == iq of an f32 object may)");
+  const bool u8 = d != nullptr && d->dtype == SDR_IQ_U8;
+  TRY(capture_check_call("sdr_iqc_process_dev", d, "iq", iq, u8 ? 2 : 8, n, out, !u8));
+  const uintptr_t a0 = (uintptr_t)iq, o0 = (uintptr_t)out;
   sdr_ctx* c = d->ctx;
   TRY(set_dev(c));
-  const bool timing = d->timing && estimate;
-  if (timing) HIP_TRY(hipEventRecord(d->ev[0], c->stream));
+  auto mark = [&](int k) { return estimate ? d->tm.mark(k, c->stream) : hipSuccess; };   // only calls with all three launches are timed
+  HIP_TRY(mark(0));
   if (estimate) {
     // at most IQC_MAX_WG chunks of whole 16-B vectors, none shorter than SDR_IQC_CHUNK but the last
     int64_t chunk;
@@ -400,11 +335,11 @@ int sdr_iqc_process_dev(sdr_iqc* d, const void* iq, int64_t n, float* out, int e
     if (u8) hipLaunchKernelGGL(iqc_moments_kernel<true>, dim3(nwg), dim3(IQC_THREADS), 0, c->stream, iq, n, chunk, d->part);
     else hipLaunchKernelGGL(iqc_moments_kernel<false>, dim3(nwg), dim3(IQC_THREADS), 0, c->stream, iq, n, chunk, d->part);
     HIP_TRY(hipGetLastError());
-    if (timing) HIP_TRY(hipEventRecord(d->ev[1], c->stream));
+    HIP_TRY(mark(1));
     const IqcUpdate up{d->part, d->st, n, nwg, u8 ? 1 : 0, d->dc, d->balance, d->rate};
     hipLaunchKernelGGL(iqc_update_kernel, dim3(1), dim3(64), 0, c->stream, up);
     HIP_TRY(hipGetLastError());
-    if (timing) HIP_TRY(hipEventRecord(d->ev[2], c->stream));
+    HIP_TRY(mark(2));
   }
   const int head = (int)std::min<int64_t>(n, (a0 & (u8 ? 3 : 15)) != 0 ? 1 : 0);
   const int64_t npairs = (n - head) / 2;
@@ -422,15 +357,12 @@ int sdr_iqc_process_dev(sdr_iqc* d, const void* iq, int64_t n, float* out, int e
   }
 #undef IQC_APPLY
   HIP_TRY(hipGetLastError());
-  if (timing) {
-    HIP_TRY(hipEventRecord(d->ev[3], c->stream));
-    d->timed = true;
-  }
+  HIP_TRY(mark(3));
   return SDR_OK;
 }
 
 int sdr_iqc_run(sdr_iqc* d, const void* iq_host, int64_t n, float* out_host, int estimate) {
-  TRY(iqc_check_call(d, iq_host, n, out_host, "sdr_iqc_run"));
+  TRY(capture_check_call("sdr_iqc_run", d, "iq", iq_host, 0, n, out_host, false));
   sdr_ctx* c = d->ctx;
   TRY(set_dev(c));
   const size_t es = d->dtype == SDR_IQ_U8 ? 2 : 8;
@@ -440,27 +372,19 @@ int sdr_iqc_run(sdr_iqc* d, const void* iq_host, int64_t n, float* out_host, int
 
 int sdr_iqc_state(sdr_iqc* d, double* host) {
   if (d == nullptr || host == nullptr) return fail(SDR_EINVAL, "sdr_iqc_state: NULL argument");
-  TRY(set_dev(d->ctx));
-  HIP_TRY(hipMemcpyAsync(host, d->st, SDR_IQC_NSTATE * sizeof(double), hipMemcpyDeviceToHost, d->ctx->stream));
-  HIP_TRY(hipStreamSynchronize(d->ctx->stream));
-  return SDR_OK;
+  return fetch(d->ctx, d->st, SDR_IQC_NSTATE, host);
 }
 
 int sdr_iqc_set_timing(sdr_iqc* d, int on) {
   if (d == nullptr) return fail(SDR_EINVAL, "sdr_iqc_set_timing: object is NULL");
   TRY(set_dev(d->ctx));
-  if (on && !d->ev[0])
-    for (hipEvent_t& e : d->ev) HIP_TRY(hipEventCreate(&e));
-  d->timing = on != 0;
+  HIP_TRY(d->tm.enable(on != 0));
   return SDR_OK;
 }
 
 int sdr_iqc_stage_ms(sdr_iqc* d, float* ms) {
   if (d == nullptr || ms == nullptr) return fail(SDR_EINVAL, "sdr_iqc_stage_ms: NULL argument");
-  if (!d->timing || !d->timed) return fail(SDR_EINVAL, "sdr_iqc_stage_ms: no timed call with an estimate (sdr_iqc_set_timing)");
-  HIP_TRY(hipEventSynchronize(d->ev[3]));
-  for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], d->ev[k], d->ev[k + 1]));
-  return SDR_OK;
+  return d->tm.elapsed(ms, "sdr_iqc_stage_ms: no timed call with an estimate (sdr_iqc_set_timing)");
 }
 
 int sdr_iqc_coeffs_dev(sdr_iqc* d, const double** dev) {

@@ -61,9 +61,7 @@ __device__ __forceinline__ void stat_add_wave(unsigned long long* s, int k, bool
   if (s != nullptr && m != 0 && (threadIdx.x & 63) == __builtin_ctzll(m)) atomicAdd(s + k, (unsigned long long)__popcll(m));
 }
 __device__ __forceinline__ void stat_max_wave(unsigned long long* s, int k, bool on, double v) {
-  double x = on ? v : -1.0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x = fmax(x, __shfl_xor(x, o, 64));
+  const double x = wave_reduce(on ? v : -1.0, [](double a, double b) { return fmax(a, b); });
   if ((threadIdx.x & 63) == 0) stat_max(s, k, x);
 }
 
@@ -1153,8 +1151,7 @@ __device__ __forceinline__ bool spec_body(const PllJobs& P, const int bid, const
     xe_p = p;
     xe_v = V;
     if constexpr (LONG) {
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) mth = fminf(mth, __shfl_xor(mth, o, 64));
+      mth = wave_reduce(mth, [](float a, float b) { return fminf(a, b); });
       if (lane == 0) mg[wv] = mth;
     }
     const int nmiss = __syncthreads_count(miss);

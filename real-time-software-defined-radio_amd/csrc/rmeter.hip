@@ -15,14 +15,13 @@
 //       SEG = true: a chunk is G = SDR_RMETER_CHUNK / window whole windows, wave w takes windows w,
 //       w + 4, .. of it: the lanes' sums run on over the chunk, the minimum and maximum go through
 //       the butterfly once a window and lane 0 stores the piece.
-//       Either way a contiguous range is read as iqc.hip's moments pass reads its chunk: 16-B
-//       non-temporal loads from the range's first 16-B boundary on, RM_U in flight a lane, the
-//       samples before it and after the last whole vector one by one, so no access leaves the
-//       range.  Per lane: f32 max and min, the finite, non-finite and over counts, two f64
-//       accumulators (the square of an f32 value is exact in f64).  Lane partials -> xor butterfly
-//       -> the four waves through LDS in wave order -> one record per chunk.  No atomics.
-//   rmeter_fold_kernel  one wave per stream.  The records lane-strided in ascending order and the
-//       butterfly give the call's sums.  The pieces go a lane each, 64 at a time: a segmented scan
+//       Either way a contiguous range is read by sdr_chunk.h's range pass, RM_U loads in flight a
+//       lane: no access leaves the range (sdr_range.h).  Per lane: f32 max and min, the finite,
+//       non-finite and over counts, two f64 accumulators (the square of an f32 value is exact in
+//       f64).  The lane partials become one record per chunk by sdr_chunk.h's block record.  No
+//       atomics.
+//   rmeter_fold_kernel  one wave per stream.  sdr_chunk.h's fold of the records gives the call's
+//       sums.  The pieces go a lane each, 64 at a time: a segmented scan
 //       keyed by the window (piece c belongs to window c / P, so a lane knows its segment's first
 //       lane by arithmetic), started from the carried window, the pieces of four rounds loaded
 //       ahead; the lane that holds a window's last piece stores its (min, max) and bins it.  Lanes of one round that hit the same bin find
@@ -56,12 +55,24 @@ static_assert(SDR_RMETER_MAX_BINS == 1 << RM_BIN_BITS, "the match looks at every
 static_assert(SDR_RMETER_CHUNK % 4 == 0 && SDR_RMETER_SEG <= SDR_RMETER_CHUNK, "a chunk holds at least one window below SDR_RMETER_SEG");
 static_assert(SDR_RMETER_MIN_WINDOW >= 64, "a window is at least a wave's lanes");
 
-// a chunk's record; the u32 counts hold a chunk's samples (at most SDR_RMETER_CHUNK)
+__device__ __forceinline__ float vmax(float a, float b) { return b > a ? b : a; }
+__device__ __forceinline__ float vmin(float a, float b) { return b < a ? b : a; }
+
+// a chunk's record, and a call's per row; the u32 counts hold a call's samples (fewer than 2^31)
 struct RmRec {
   double sum, sumsq;
   uint32_t nfin, nonfinite, over;
   float mx, mn;
   uint32_t pad;
+  __device__ __forceinline__ void combine(const RmRec& o) {
+    nfin += o.nfin;
+    nonfinite += o.nonfinite;
+    over += o.over;
+    mx = vmax(mx, o.mx);
+    mn = vmin(mn, o.mn);
+    sum += o.sum;
+    sumsq += o.sumsq;
+  }
 };
 static_assert(sizeof(RmRec) == 40, "five 8-byte words");
 
@@ -72,19 +83,6 @@ struct RmGeom {
   int K, nrec, npiece;        // windows the call touches; records and pieces per row
   float limit;
 };
-
-__device__ __forceinline__ float vmax(float a, float b) { return b > a ? b : a; }
-__device__ __forceinline__ float vmin(float a, float b) { return b < a ? b : a; }
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = vmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = vmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // a lane's share of a range
 struct Acc {
@@ -105,35 +103,19 @@ struct Acc {
   }
 };
 
-// the samples p[0 .. len) among NL lanes, this one lane t of them: no access leaves the range
+// the samples p[0 .. len) among NL lanes, this one lane t of them (rows are aligned to one float)
 template <int NL>
-__device__ __forceinline__ void scan_range(const float* __restrict__ p, int64_t len, int t, float limit, Acc& a) {
-  const int mis = (int)((uintptr_t)p & 15);                          // a multiple of 4: rows are aligned to one float
-  const int64_t h = mis ? (16 - mis) / 4 : 0;
-  const int head = (int)(h < len ? h : len);
-  const int64_t nv = (len - head) / 4;
-  const int tail = (int)(len - head - 4 * nv);
-  const u4* __restrict__ v = reinterpret_cast<const u4*>(p + head);
-  for (int64_t i0 = t; i0 < nv; i0 += NL * RM_U) {
-    u4 x[RM_U];
-    bool in[RM_U];
-#pragma unroll
-    for (int u = 0; u < RM_U; ++u) {
-      in[u] = i0 + NL * u < nv;
-      x[u] = in[u] ? __builtin_nontemporal_load(v + i0 + NL * u) : u4{0u, 0u, 0u, 0u};
-    }
-#pragma unroll
-    for (int u = 0; u < RM_U; ++u)
-      if (in[u]) {
-        const f4 f = __builtin_bit_cast(f4, x[u]);
+__device__ __forceinline__ void scan_row(const float* __restrict__ p, int64_t len, int t, float limit, Acc& a) {
+  scan_range<4, NL, RM_U>(
+      reinterpret_cast<const char*>(p), split_range<4>((uintptr_t)p, len), t,
+      [&](const u4 x, int64_t) {
+        const f4 f = __builtin_bit_cast(f4, x);
         a.add(f.x, limit);
         a.add(f.y, limit);
         a.add(f.z, limit);
         a.add(f.w, limit);
-      }
-  }
-  if (t < head) a.add(p[t], limit);
-  if (t < tail) a.add(p[head + 4 * nv + t], limit);
+      },
+      [&](const char* q) { a.add(*reinterpret_cast<const float*>(q), limit); });
 }
 
 template <bool SEG>
@@ -152,7 +134,7 @@ __global__ __launch_bounds__(RM_THREADS) void rmeter_reduce_kernel(const float* 
       hi = hi < g.n ? hi : g.n;
       a.mx = -INFINITY;
       a.mn = INFINITY;
-      scan_range<64>(row + lo, hi - lo, lane, g.limit, a);
+      scan_row<64>(row + lo, hi - lo, lane, g.limit, a);
       const float mx = wave_max(a.mx), mn = wave_min(a.mn);
       if (lane == 0) pc[k] = f2{mn, mx};
       cmx = vmax(cmx, mx);
@@ -165,36 +147,12 @@ __global__ __launch_bounds__(RM_THREADS) void rmeter_reduce_kernel(const float* 
     const int64_t base = (int64_t)k * g.W - g.w0;
     const int64_t o0 = (int64_t)p * g.L < g.W ? (int64_t)p * g.L : g.W, o1 = o0 + g.L < g.W ? o0 + g.L : g.W;
     const int64_t lo = base + o0 > 0 ? base + o0 : 0, hi = base + o1 < g.n ? base + o1 : g.n;
-    if (hi > lo) scan_range<RM_THREADS>(row + lo, hi - lo, (int)threadIdx.x, g.limit, a);
+    if (hi > lo) scan_row<RM_THREADS>(row + lo, hi - lo, (int)threadIdx.x, g.limit, a);
   }
-  // lane partials -> one record per chunk, in a fixed order
-  __shared__ RmRec wp[RM_WAVES];
-  RmRec r;
-  r.nfin = wave_sum64(a.nfin);
-  r.nonfinite = wave_sum64(a.nonfinite);
-  r.over = wave_sum64(a.over);
-  r.mx = wave_max(a.mx);
-  r.mn = wave_min(a.mn);
-  r.sum = wave_sum64(a.s);
-  r.sumsq = wave_sum64(a.q);
-  r.pad = 0;
-  if (lane == 0) wp[w] = r;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    r = wp[0];
-#pragma unroll
-    for (int j = 1; j < RM_WAVES; ++j) {
-      r.nfin += wp[j].nfin;
-      r.nonfinite += wp[j].nonfinite;
-      r.over += wp[j].over;
-      r.mx = vmax(r.mx, wp[j].mx);
-      r.mn = vmin(r.mn, wp[j].mn);
-      r.sum += wp[j].sum;
-      r.sumsq += wp[j].sumsq;
-    }
+  block_record<RM_WAVES>(RmRec{a.s, a.q, a.nfin, a.nonfinite, a.over, a.mx, a.mn, 0}, [&](const RmRec& r) {
     rec[(int64_t)blockIdx.y * g.nrec + blockIdx.x] = r;
     if constexpr (!SEG) pc[blockIdx.x] = f2{r.mn, r.mx};
-  }
+  });
 }
 
 struct RmFold {
@@ -212,34 +170,9 @@ __global__ __launch_bounds__(64) void rmeter_fold_kernel(const RmFold a) {
   __shared__ uint32_t lh[SDR_RMETER_MAX_BINS];     // the call's share of the histogram
   const int lane = threadIdx.x, s = blockIdx.x;
   sdr_rmeter_record* st = a.st + s;
-  // the call's sums: the records lane-strided in ascending order, then the butterfly
+  // the call's sums
   const RmRec* __restrict__ r = a.rec + (int64_t)s * a.nrec;
-  unsigned long long nfin = 0, nonfinite = 0, over = 0;
-  float mx = -INFINITY, mn = INFINITY;
-  double S = 0.0, Q = 0.0;
-  for (int b0 = lane; b0 < a.nrec; b0 += 64 * RM_FOLD_U) {
-    RmRec x[RM_FOLD_U];
-#pragma unroll
-    for (int u = 0; u < RM_FOLD_U; ++u) x[u] = r[b0 + 64 * u < a.nrec ? b0 + 64 * u : a.nrec - 1];   // every load is issued: no branch around it
-#pragma unroll
-    for (int u = 0; u < RM_FOLD_U; ++u)
-      if (b0 + 64 * u < a.nrec) {
-        nfin += x[u].nfin;
-        nonfinite += x[u].nonfinite;
-        over += x[u].over;
-        mx = vmax(mx, x[u].mx);
-        mn = vmin(mn, x[u].mn);
-        S += x[u].sum;
-        Q += x[u].sumsq;
-      }
-  }
-  nfin = wave_sum64(nfin);
-  nonfinite = wave_sum64(nonfinite);
-  over = wave_sum64(over);
-  mx = wave_max(mx);
-  mn = wave_min(mn);
-  S = wave_sum64(S);
-  Q = wave_sum64(Q);
+  const RmRec sum = fold_records<RM_FOLD_U>(a.nrec, lane, RmRec{0.0, 0.0, 0, 0, 0, -INFINITY, INFINITY, 0}, [&](int b) { return r[b]; });
 
   for (int b = lane; b < a.nbins; b += 64) lh[b] = 0;
   __syncthreads();
@@ -314,26 +247,26 @@ __global__ __launch_bounds__(64) void rmeter_fold_kernel(const RmFold a) {
     const uint32_t add = lh[b];
     if (add != 0) hist[b] += add;
   }
-  empty = wave_sum64(empty);
+  empty = wave_sum(empty);
   if (lane != 0) return;
-  st->n = (int64_t)nfin;
-  st->nonfinite = (int64_t)nonfinite;
-  st->over = (int64_t)over;
+  st->n = sum.nfin;
+  st->nonfinite = sum.nonfinite;
+  st->over = sum.over;
   st->windows = a.Kc;
-  st->sum = S;
-  st->sumsq = Q;
-  st->max = mx;
-  st->min = mn;
+  st->sum = sum.sum;
+  st->sumsq = sum.sumsq;
+  st->max = sum.mx;
+  st->min = sum.mn;
   st->calls += 1;
-  st->total_n += (int64_t)nfin;
-  st->total_nonfinite += (int64_t)nonfinite;
-  st->total_over += (int64_t)over;
+  st->total_n += sum.nfin;
+  st->total_nonfinite += sum.nonfinite;
+  st->total_over += sum.over;
   st->total_windows += a.Kc;
   st->empty_windows += empty;
-  st->total_sum += S;
-  st->total_sumsq += Q;
-  st->total_max = vmax(st->total_max, mx);
-  st->total_min = vmin(st->total_min, mn);
+  st->total_sum += sum.sum;
+  st->total_sumsq += sum.sumsq;
+  st->total_max = vmax(st->total_max, sum.mx);
+  st->total_min = vmin(st->total_min, sum.mn);
   st->wcount = a.wcount;
   if (a.wcount == 0) {                                                // the call ended on a boundary
     st->wmin = INFINITY;
@@ -360,31 +293,15 @@ struct sdr_rmeter {
   sdr_rmeter_params prm = {};
   int64_t pos = 0;                     // samples per stream since the last reset
   int64_t last_windows = 0, wstride = 1;   // of the latest call
+  DevMem mem;
   sdr_rmeter_record* st = nullptr;     // [S]
   unsigned long long* hist = nullptr;  // [S][nbins]
-  RmRec* rec = nullptr;                // the work arrays, grown to the largest call
-  f2* piece = nullptr;
-  f2* win = nullptr;
-  size_t rec_cap = 0, piece_cap = 0, win_cap = 0;   // elements
-  bool timing = false, timed = false;
-  hipEvent_t ev[3] = {};
+  GrowMem<RmRec> rec;                  // the work arrays, grown to the largest call
+  GrowMem<f2> piece, win;
+  StageTimer<2> tm;                    // around the two launches of a call (sdr_rmeter_set_timing)
 };
 
 namespace {
-
-// a work array of at least `need` elements; growing it waits for the calls in flight
-template <class T>
-int rm_grow(sdr_rmeter* d, T** p, size_t* cap, size_t need) {
-  if (need <= *cap) return SDR_OK;
-  HIP_TRY(hipStreamSynchronize(d->ctx->stream));
-  (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const hipError_t e = hipMalloc(p, need * sizeof(T));
-  if (e != hipSuccess) return create_failed(e, "sdr_rmeter_process_dev");
-  *cap = need;
-  return SDR_OK;
-}
 
 // the call-time rules, for host and device rows alike
 int rm_check_call(const sdr_rmeter* d, const float* rows, int64_t stride, int64_t n, const char* what) {
@@ -419,13 +336,9 @@ int sdr_rmeter_create(sdr_ctx* c, int nstreams, const sdr_rmeter_params* params,
   d->ctx = c;
   d->S = nstreams;
   d->prm = *params;
-  hipError_t e = hipMalloc(&d->st, (size_t)nstreams * sizeof(sdr_rmeter_record));
-  if (e == hipSuccess) e = hipMalloc(&d->hist, (size_t)nstreams * params->nbins * sizeof(unsigned long long));
-  if (e != hipSuccess) {
-    sdr_rmeter_destroy(d);
-    return create_failed(e, "sdr_rmeter_create");
-  }
-  const int rc = sdr_rmeter_reset(d);
+  d->mem.get(&d->st, (size_t)nstreams);
+  d->mem.get(&d->hist, (size_t)nstreams * params->nbins);
+  const int rc = d->mem.err != hipSuccess ? create_failed(d->mem.err, "sdr_rmeter_create") : sdr_rmeter_reset(d);
   if (rc != SDR_OK) {
     sdr_rmeter_destroy(d);
     return rc;
@@ -437,13 +350,10 @@ int sdr_rmeter_create(sdr_ctx* c, int nstreams, const sdr_rmeter_params* params,
 void sdr_rmeter_destroy(sdr_rmeter* d) {
   if (d == nullptr) return;
   if (d->ctx != nullptr && set_dev(d->ctx) == SDR_OK) (void)hipStreamSynchronize(d->ctx->stream);
-  for (hipEvent_t e : d->ev)
-    if (e) (void)hipEventDestroy(e);
-  (void)hipFree(d->st);
-  (void)hipFree(d->hist);
-  (void)hipFree(d->rec);
-  (void)hipFree(d->piece);
-  (void)hipFree(d->win);
+  d->mem.release();
+  d->rec.release();
+  d->piece.release();
+  d->win.release();
   delete d;
 }
 
@@ -483,23 +393,19 @@ int sdr_rmeter_process_dev(sdr_rmeter* d, const float* rows, int64_t stride, int
     g.nrec = g.npiece = (int)(K * g.P);
   }
   const int64_t wstride = std::max<int64_t>(Kc, 1);
-  TRY(rm_grow(d, &d->rec, &d->rec_cap, (size_t)d->S * g.nrec));
-  TRY(rm_grow(d, &d->piece, &d->piece_cap, (size_t)d->S * g.npiece));
-  TRY(rm_grow(d, &d->win, &d->win_cap, (size_t)d->S * wstride));
-  const bool timing = d->timing;
-  if (timing) HIP_TRY(hipEventRecord(d->ev[0], c->stream));
+  TRY(d->rec.fit((size_t)d->S * g.nrec, c->stream, "sdr_rmeter_process_dev"));
+  TRY(d->piece.fit((size_t)d->S * g.npiece, c->stream, "sdr_rmeter_process_dev"));
+  TRY(d->win.fit((size_t)d->S * wstride, c->stream, "sdr_rmeter_process_dev"));
+  HIP_TRY(d->tm.mark(0, c->stream));
   const dim3 grid((unsigned)g.nrec, (unsigned)d->S);
-  if (seg) hipLaunchKernelGGL(rmeter_reduce_kernel<true>, grid, dim3(RM_THREADS), 0, c->stream, rows, g, d->rec, d->piece);
-  else hipLaunchKernelGGL(rmeter_reduce_kernel<false>, grid, dim3(RM_THREADS), 0, c->stream, rows, g, d->rec, d->piece);
+  if (seg) hipLaunchKernelGGL(rmeter_reduce_kernel<true>, grid, dim3(RM_THREADS), 0, c->stream, rows, g, d->rec.p, d->piece.p);
+  else hipLaunchKernelGGL(rmeter_reduce_kernel<false>, grid, dim3(RM_THREADS), 0, c->stream, rows, g, d->rec.p, d->piece.p);
   HIP_TRY(hipGetLastError());
-  if (timing) HIP_TRY(hipEventRecord(d->ev[1], c->stream));
-  const RmFold f{d->rec, d->piece, d->st, d->hist, d->win, wstride, (w0 + n) % W, g.nrec, g.npiece, g.P, (int)Kc, d->prm.nbins, d->prm.scale};
+  HIP_TRY(d->tm.mark(1, c->stream));
+  const RmFold f{d->rec.p, d->piece.p, d->st, d->hist, d->win.p, wstride, (w0 + n) % W, g.nrec, g.npiece, g.P, (int)Kc, d->prm.nbins, d->prm.scale};
   hipLaunchKernelGGL(rmeter_fold_kernel, dim3(d->S), dim3(64), 0, c->stream, f);
   HIP_TRY(hipGetLastError());
-  if (timing) {
-    HIP_TRY(hipEventRecord(d->ev[2], c->stream));
-    d->timed = true;
-  }
+  HIP_TRY(d->tm.mark(2, c->stream));
   d->pos += n;
   d->last_windows = Kc;
   d->wstride = wstride;
@@ -510,31 +416,18 @@ int sdr_rmeter_run(sdr_rmeter* d, const float* rows_host, int64_t stride, int64_
   TRY(rm_check_call(d, rows_host, stride, n, "sdr_rmeter_run"));
   sdr_ctx* c = d->ctx;
   TRY(set_dev(c));
-  void* din = nullptr;
-  TRY(scratch(c, S_IN, (size_t)d->S * n * 4, &din));
-  if (d->S == 1)
-    HIP_TRY(hipMemcpyAsync(din, rows_host, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  else
-    HIP_TRY(hipMemcpy2DAsync(din, (size_t)n * 4, rows_host, (size_t)stride * 4, (size_t)n * 4, d->S, hipMemcpyHostToDevice, c->stream));
-  TRY(sdr_rmeter_process_dev(d, (const float*)din, n, n));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return SDR_OK;
+  return run_staged(c, rows_host, {(size_t)d->S, (size_t)n * 4, (size_t)stride * 4}, nullptr, {},
+                    [&](void* din, void*) { return sdr_rmeter_process_dev(d, (const float*)din, n, n); });
 }
 
 int sdr_rmeter_records(sdr_rmeter* d, sdr_rmeter_record* host) {
   if (d == nullptr || host == nullptr) return fail(SDR_EINVAL, "sdr_rmeter_records: NULL argument");
-  TRY(set_dev(d->ctx));
-  HIP_TRY(hipMemcpyAsync(host, d->st, (size_t)d->S * sizeof(sdr_rmeter_record), hipMemcpyDeviceToHost, d->ctx->stream));
-  HIP_TRY(hipStreamSynchronize(d->ctx->stream));
-  return SDR_OK;
+  return fetch(d->ctx, d->st, (size_t)d->S, host);
 }
 
 int sdr_rmeter_hist(sdr_rmeter* d, uint64_t* host) {
   if (d == nullptr || host == nullptr) return fail(SDR_EINVAL, "sdr_rmeter_hist: NULL argument");
-  TRY(set_dev(d->ctx));
-  HIP_TRY(hipMemcpyAsync(host, d->hist, (size_t)d->S * d->prm.nbins * 8, hipMemcpyDeviceToHost, d->ctx->stream));
-  HIP_TRY(hipStreamSynchronize(d->ctx->stream));
-  return SDR_OK;
+  return fetch(d->ctx, reinterpret_cast<const uint64_t*>(d->hist), (size_t)d->S * d->prm.nbins, host);
 }
 
 int sdr_rmeter_windows(sdr_rmeter* d, float* host, int64_t cap, int64_t* counts) {
@@ -543,7 +436,7 @@ int sdr_rmeter_windows(sdr_rmeter* d, float* host, int64_t cap, int64_t* counts)
   TRY(set_dev(d->ctx));
   const int64_t take = std::min(cap, d->last_windows);
   if (take > 0)
-    HIP_TRY(hipMemcpy2DAsync(host, (size_t)cap * 8, d->win, (size_t)d->wstride * 8, (size_t)take * 8, d->S, hipMemcpyDeviceToHost, d->ctx->stream));
+    HIP_TRY(hipMemcpy2DAsync(host, (size_t)cap * 8, d->win.p, (size_t)d->wstride * 8, (size_t)take * 8, d->S, hipMemcpyDeviceToHost, d->ctx->stream));
   HIP_TRY(hipStreamSynchronize(d->ctx->stream));
   if (counts != nullptr)
     for (int s = 0; s < d->S; ++s) counts[s] = d->last_windows;      // the streams share the position
@@ -560,18 +453,13 @@ int sdr_rmeter_state_dev(sdr_rmeter* d, const sdr_rmeter_record** dev, const uin
 int sdr_rmeter_set_timing(sdr_rmeter* d, int on) {
   if (d == nullptr) return fail(SDR_EINVAL, "sdr_rmeter_set_timing: object is NULL");
   TRY(set_dev(d->ctx));
-  if (on && !d->ev[0])
-    for (hipEvent_t& e : d->ev) HIP_TRY(hipEventCreate(&e));
-  d->timing = on != 0;
+  HIP_TRY(d->tm.enable(on != 0));
   return SDR_OK;
 }
 
 int sdr_rmeter_stage_ms(sdr_rmeter* d, float* ms) {
   if (d == nullptr || ms == nullptr) return fail(SDR_EINVAL, "sdr_rmeter_stage_ms: NULL argument");
-  if (!d->timing || !d->timed) return fail(SDR_EINVAL, "sdr_rmeter_stage_ms: no timed call (sdr_rmeter_set_timing)");
-  HIP_TRY(hipEventSynchronize(d->ev[2]));
-  for (int k = 0; k < 2; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], d->ev[k], d->ev[k + 1]));
-  return SDR_OK;
+  return d->tm.elapsed(ms, "sdr_rmeter_stage_ms: no timed call (sdr_rmeter_set_timing)");
 }
 
 }  // extern "C"

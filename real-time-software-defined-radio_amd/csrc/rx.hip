@@ -92,8 +92,7 @@ struct sdr_rx : RxLayout {             // M, A, R, the rows' lengths and strides
     size_t region[SDR_RX_NOUTPUTS] = {};
   } pq[4];                             // depth + 1 at most (the new block before k-depth leaves)
   int pq_head = 0, pq_n = 0;
-  bool timing = false;                 // events between the stages of each block
-  hipEvent_t ev[SDR_RX_NSTAGES + 1] = {};
+  StageTimer<SDR_RX_NSTAGES> tm;       // events between the stages of each block (sdr_rx_set_timing)
   // outputs process_dev materialises (sdr_rx_set_keep; bit o = SDR_RX_O_o): the NCO rows and
   // the RDS LPF rows are intermediates the chain does not need (the mixers form the NCO from
   // the PLL phases, the RDS LPF runs inside the composite resampler)
@@ -252,7 +251,7 @@ void sdr_rx_destroy(sdr_rx* r) {
   for (void* p : {r->pin_in, (void*)r->pin_out})
     if (p) (void)hipHostFree(p);
   auto drop = [](auto& evs) { for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e); };
-  drop(r->ev); drop(r->ev_front); drop(r->ev_mid); drop(r->ev_back); drop(r->ev_done);
+  drop(r->ev_front); drop(r->ev_mid); drop(r->ev_back); drop(r->ev_done);
   if (r->front) (void)hipStreamDestroy(r->front);
   if (r->mid) (void)hipStreamDestroy(r->mid);
   delete r;
@@ -304,6 +303,7 @@ int sdr_rx_reset(sdr_rx* r) {
   if (r->bl) TRY(sdr_blend_reset(r->bl));
   HIP_TRY(hipStreamSynchronize(st));
   r->parity = 0; r->blocks = 0;
+  r->tm.timed = false;                           // the blocks before the reset are gone
   r->last_fs = nullptr; r->host_done = -1;
   std::memcpy(r->out, r->outs[0], sizeof r->out);
   r->pcm = r->pcms[0];
@@ -402,7 +402,7 @@ struct RxBlock {
 };
 
 bool kept(const sdr_rx* r, int o) { return (r->keep_now >> o) & 1ull; }
-hipError_t mark(const sdr_rx* r, int k, hipStream_t s) { return r->timing ? hipEventRecord(r->ev[k], s) : hipSuccess; }
+hipError_t mark(sdr_rx* r, int k, hipStream_t s) { return r->tm.mark(k, s); }
 const double* zin(const RxBlock& b, int z) { return b.zi + b.r->zoff[z]; }
 double* zout(const RxBlock& b, int z) { return b.zf + b.r->zoff[z]; }
 // block k-nq, the last on this row set, may still run (not when the host has waited for it: submissions)
@@ -927,18 +927,13 @@ int sdr_rx_fetch(sdr_rx* r, int which, float* host, int64_t host_stride) {
 int sdr_rx_set_timing(sdr_rx* r, int on) {
   CHECK_RX(r);
   TRY(set_dev(r->c));
-  if (on && !r->ev[0])
-    for (hipEvent_t& e : r->ev) HIP_TRY(hipEventCreate(&e));
-  r->timing = on != 0;
+  HIP_TRY(r->tm.enable(on != 0));
   return SDR_OK;
 }
 
 int sdr_rx_stage_ms(sdr_rx* r, float* ms) {
   if (r == nullptr || ms == nullptr) return fail(SDR_EINVAL, "sdr_rx_stage_ms: NULL argument");
-  if (!r->timing || r->blocks == 0) return fail(SDR_EINVAL, "sdr_rx_stage_ms: no timed block (sdr_rx_set_timing)");
-  HIP_TRY(hipEventSynchronize(r->ev[SDR_RX_NSTAGES]));
-  for (int k = 0; k < SDR_RX_NSTAGES; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], r->ev[k], r->ev[k + 1]));
-  return SDR_OK;
+  return r->tm.elapsed(ms, "sdr_rx_stage_ms: no timed block (sdr_rx_set_timing)");
 }
 
 int sdr_rx_pll_stats(sdr_rx* r, int64_t* out, int reset) {

@@ -336,17 +336,25 @@ struct OutQ3 {
   }
 };
 
-// Wave-wide sum over 64 lanes (CDNA wave64: six xor steps).
-__device__ __forceinline__ float wave_sum(float v) {
+// Wave-wide reduction over 64 lanes (CDNA wave64): v = op(v, the other lane's v) over the xor
+// steps 32, 16, .., 1, the same order in every lane -- floating-point results depend on it.
+template <class T, class Op>
+__device__ __forceinline__ T wave_reduce(T v, Op op) {
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
   return v;
 }
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+  return wave_reduce(v, [](T a, T b) { return a + b; });
+}
+template <class T>
+__device__ __forceinline__ T wave_max(T v) {
+  return wave_reduce(v, [](T a, T b) { return b > a ? b : a; });
+}
+template <class T>
+__device__ __forceinline__ T wave_min(T v) {
+  return wave_reduce(v, [](T a, T b) { return b < a ? b : a; });
 }
 
 // XCD-aware tile order: hardware deals workgroups round-robin over the 8 XCDs

@@ -193,14 +193,93 @@ struct DevMem {
   }
 };
 
-// an object's per-stream struct array on the host, after waiting for the calls in flight
+// A work array that grows to the largest call: at least `need` elements after fit().  Growing
+// waits for the calls in flight on `st`, which may still read the old array.
 template <class T>
-int fetch_states(sdr_ctx* c, const T* dev, int nstreams, std::vector<T>* out) {
+struct GrowMem {
+  T* p = nullptr;
+  size_t cap = 0;   // elements
+  int fit(size_t need, hipStream_t st, const char* what) {
+    if (need <= cap) return SDR_OK;
+    HIP_TRY(hipStreamSynchronize(st));
+    release();
+    const hipError_t e = hipMalloc(&p, need * sizeof(T));
+    if (e != hipSuccess) return create_failed(e, what);
+    cap = need;
+    return SDR_OK;
+  }
+  void release() {
+    (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+// HIP events around the N launches (stages) of a call: mark(k) in front of stage k, mark(N) behind
+// the last.  Off until enable(true), which creates the events.
+template <int N>
+struct StageTimer {
+  bool on = false, timed = false;   // timed: a call has been marked to its end
+  hipEvent_t ev[N + 1] = {};
+  ~StageTimer() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  hipError_t enable(bool want) {
+    if (want && !ev[0])
+      for (hipEvent_t& e : ev) {
+        const hipError_t err = hipEventCreate(&e);
+        if (err != hipSuccess) return err;
+      }
+    on = want;
+    return hipSuccess;
+  }
+  hipError_t mark(int k, hipStream_t st) {
+    if (!on) return hipSuccess;
+    const hipError_t err = hipEventRecord(ev[k], st);
+    if (k == N && err == hipSuccess) timed = true;
+    return err;
+  }
+  // ms[0..N) of the latest call marked to its end, after waiting for it; `refusal` is the error
+  // text where there is none
+  int elapsed(float* ms, const char* refusal) {
+    if (!on || !timed) return fail(SDR_EINVAL, "%s", refusal);
+    HIP_TRY(hipEventSynchronize(ev[N]));
+    for (int k = 0; k < N; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+    return SDR_OK;
+  }
+};
+
+// The call-time rules of a pass over a capture block (iqc, ingest): n complex samples of es bytes
+// at `raw` -- `name` in the messages -- to n complex f32 at out.  es = 0: host buffers, which need
+// no alignment and are staged apart.  in_place_ok: out == raw is the one overlap allowed.
+inline int capture_check_call(const char* what, const void* obj, const char* name, const void* raw, int es, int64_t n, const float* out,
+                              bool in_place_ok) {
+  if (obj == nullptr) return fail(SDR_EINVAL, "%s: object is NULL", what);
+  if (raw == nullptr || out == nullptr) return fail(SDR_EINVAL, "%s: %s or out is NULL", what, name);
+  if (n < 1 || n > INT32_MAX) return fail(SDR_EINVAL, "%s: n=%lld outside [1, 2^31 - 1]", what, (long long)n);
+  if (es == 0) return SDR_OK;
+  const uintptr_t a0 = (uintptr_t)raw, a1 = a0 + (uintptr_t)n * es, o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)n * 8;
+  if ((a0 & (es - 1)) != 0 || (o0 & 7) != 0)
+    return fail(SDR_EINVAL, "%s: %s must be aligned to one complex sample (%d B) and out to 8 B", what, name, es);
+  if (a0 < o1 && o0 < a1 && !(in_place_ok && a0 == o0))
+    return fail(SDR_EINVAL, "%s: %s and out overlap (only out == %s of an f32 object may)", what, name, name);
+  return SDR_OK;
+}
+
+// count elements of a device array on the host, after waiting for the calls in flight
+template <class T>
+int fetch(sdr_ctx* c, const T* dev, size_t count, T* host) {
   TRY(set_dev(c));
-  out->resize((size_t)nstreams);
-  HIP_TRY(hipMemcpyAsync(out->data(), dev, sizeof(T) * out->size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return SDR_OK;
+}
+// an object's per-stream struct array
+template <class T>
+int fetch_states(sdr_ctx* c, const T* dev, int nstreams, std::vector<T>* out) {
+  out->resize((size_t)nstreams);
+  return fetch(c, dev, out->size(), out->data());
 }
 
 // rows of row_bytes bytes each; on the host `pitch` bytes apart, packed on the device
@@ -208,18 +287,20 @@ struct HostRows {
   size_t rows, row_bytes, pitch;
 };
 // A synchronous host call of a block: the input rows to context slot S_IN, call(din, dout) -- the
-// block's process_dev on packed rows --, the output rows back from S_OUT, one wait.
+// block's process_dev on packed rows --, the output rows back from S_OUT (out_host NULL: the block
+// has none, dout is NULL), one wait.
 template <class F>
 int run_staged(sdr_ctx* c, const void* in_host, HostRows in, void* out_host, HostRows out, F&& call) {
   void *din = nullptr, *dout = nullptr;
   TRY(scratch(c, S_IN, in.rows * in.row_bytes, &din));
-  TRY(scratch(c, S_OUT, out.rows * out.row_bytes, &dout));
+  if (out_host != nullptr) TRY(scratch(c, S_OUT, out.rows * out.row_bytes, &dout));
   if (in.rows == 1)
     HIP_TRY(hipMemcpyAsync(din, in_host, in.row_bytes, hipMemcpyHostToDevice, c->stream));
   else
     HIP_TRY(hipMemcpy2DAsync(din, in.row_bytes, in_host, in.pitch, in.row_bytes, in.rows, hipMemcpyHostToDevice, c->stream));
   TRY(call(din, dout));
-  HIP_TRY(hipMemcpy2DAsync(out_host, out.pitch, dout, out.row_bytes, out.row_bytes, out.rows, hipMemcpyDeviceToHost, c->stream));
+  if (out_host != nullptr)
+    HIP_TRY(hipMemcpy2DAsync(out_host, out.pitch, dout, out.row_bytes, out.row_bytes, out.rows, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return SDR_OK;
 }

@@ -1,8 +1,10 @@
 """What the blocks' timing tools share (ddc_time, pfb_time, rsmp_time, spectrum_time, rspec_time,
-iqc_time, blend_time, rds_link_time, rds_sync_time, rds_clock_time, rds_carrier_time): the
-HIP-event loop, best and median of its repeats, the parser of a build's kernel resource remarks
-and the copy bandwidth of the box."""
+iqc_time, ingest_time, rmeter_time, blend_time, rds_link_time, rds_sync_time, rds_clock_time,
+rds_carrier_time): the HIP-event loop, best and median (and p90) of its repeats, the parser of a
+build's kernel resource remarks, the copy and read bandwidth of the box and the way a result
+leaves as one JSON line."""
 import ctypes
+import json
 import os
 import re
 import sys
@@ -47,10 +49,13 @@ def event_ms(ctx, calls, reps, warmup, before=None):
     return [np.array(v) for v in ms]
 
 
-def stats(ms):
-    """Best and median of the repeats, in microseconds."""
+def stats(ms, p90=False):
+    """Best and median of the repeats, in microseconds; p90: and their 90th percentile."""
     ms = np.asarray(ms)
-    return {"best_us": round(float(ms.min()) * 1e3, 1), "median_us": round(float(np.median(ms)) * 1e3, 1)}
+    out = {"best_us": round(float(ms.min()) * 1e3, 1), "median_us": round(float(np.median(ms)) * 1e3, 1)}
+    if p90:
+        out["p90_us"] = round(float(np.percentile(ms, 90)) * 1e3, 1)
+    return out
 
 
 def kernel_resources(path, pattern, label, fields):
@@ -77,8 +82,27 @@ def mma_label(kernel):
                       f"{'A in LDS' if m.group(3) == '1' else 'A from L2'}>")
 
 
-def copy_gbs(ctx, nbytes=256 << 20):
-    """GB/s (read + write) of the box's copy kernel over nbytes (sdr_copy_bandwidth)."""
+def _probe_gbs(ctx, name, nbytes, reps):
     gbs = ctypes.c_double(0.0)
-    rtsdr._lib.check(ctx.lib.sdr_copy_bandwidth(ctx.handle, int(nbytes), 20, ctypes.byref(gbs)), "sdr_copy_bandwidth")
+    rtsdr._lib.check(getattr(ctx.lib, name)(ctx.handle, int(nbytes), int(reps), ctypes.byref(gbs)), name)
     return gbs.value
+
+
+def copy_gbs(ctx, nbytes=256 << 20, reps=20):
+    """GB/s (read + write) of the box's copy kernel over nbytes (sdr_copy_bandwidth), best of reps."""
+    return _probe_gbs(ctx, "sdr_copy_bandwidth", nbytes, reps)
+
+
+def read_gbs(ctx, nbytes, reps=20):
+    """GB/s of the box's read-only stream probe over nbytes (sdr_read_bandwidth), best of reps."""
+    return _probe_gbs(ctx, "sdr_read_bandwidth", nbytes, reps)
+
+
+def emit(res, out=None):
+    """Print the result as one JSON line; `out`: also write it to that file."""
+    line = json.dumps(res)
+    print(line)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(line + "\n")

@@ -17,8 +17,6 @@ JSON line.
                               [--res real-time-software-defined-radio_amd/_build/ingest.res]
 """
 import argparse
-import json
-import os
 
 import numpy as np
 
@@ -106,12 +104,7 @@ def main():
            "kernels": bt.kernel_resources(a.res, r"(ingest_(?:fold_)?kernel)(?:ILi(\d)ELb(\d)ELb(\d)E)?", label,
                                           ("vgprs", "scratch", "occupancy", "static_lds")),
            "formats": [one_format(ctx, n, fmt, bits, a.reps, a.warmup) for fmt, bits in FORMATS]}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    bt.emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -18,9 +18,6 @@ plus noise with the impairment of tests/iqc_capture.py, tiled.  One JSON line.
                            [--res real-time-software-defined-radio_amd/_build/iqc.res]
 """
 import argparse
-import ctypes
-import json
-import os
 from importlib import import_module
 
 import numpy as np
@@ -46,11 +43,6 @@ def make_capture(n, u8):
     x[1::2] = 1.06 * (z.imag * np.cos(th) + z.real * np.sin(th)) - 0.02
     x = (np.rint(128.0 * x) + 128.0).astype(np.uint8) if u8 else x.astype(np.float32)
     return np.tile(x, -(-n // m))[:2 * n]
-
-
-def stats(ms):
-    ms = np.asarray(ms)
-    return {"best_us": round(float(ms.min()) * 1e3, 1), "median_us": round(float(np.median(ms)) * 1e3, 1)}
 
 
 def ulps(a, b):
@@ -84,12 +76,6 @@ def verify(corr, x, din, dout, n, u8):
             "rows_differing_share": float(np.mean(y != ref))}
 
 
-def probe(ctx, fn, nbytes, reps):
-    g = ctypes.c_double(0.0)
-    rtsdr._lib.check(fn(ctx.handle, int(nbytes), reps, ctypes.byref(g)), "bandwidth probe")
-    return g.value
-
-
 def one_type(ctx, n, u8, reps, warmup):
     dt = np.uint8 if u8 else np.float32
     es = 2 if u8 else 8
@@ -107,9 +93,9 @@ def one_type(ctx, n, u8, reps, warmup):
             parts[k].append(v)
     corr.set_timing(False)
     apply_bytes, moments_bytes = (es + 8) * n, es * n
-    copy_gbs = probe(ctx, ctx.lib.sdr_copy_bandwidth, apply_bytes // 2, reps)      # reads and writes that many each
-    read_gbs = probe(ctx, ctx.lib.sdr_read_bandwidth, moments_bytes, reps)
-    res.update({"call": stats(whole), "apply_only": stats(apply_only), "launches": {k: stats(v) for k, v in parts.items()},
+    copy_gbs = bt.copy_gbs(ctx, apply_bytes // 2, reps)                            # reads and writes that many each
+    read_gbs = bt.read_gbs(ctx, moments_bytes, reps)
+    res.update({"call": bt.stats(whole), "apply_only": bt.stats(apply_only), "launches": {k: bt.stats(v) for k, v in parts.items()},
                 "apply_bytes": apply_bytes, "moments_bytes": moments_bytes, "call_bytes": apply_bytes + moments_bytes,
                 "copy_probe_gbs": round(copy_gbs, 1), "copy_probe_us": round(apply_bytes / copy_gbs / 1e3, 1),
                 "read_probe_gbs": round(read_gbs, 1), "read_probe_us": round(moments_bytes / read_gbs / 1e3, 1)})
@@ -140,12 +126,7 @@ def main():
                                           + ("" if m.group(3) is None else ",out16" if m.group(3) == "1" else ",out8"),
                                           ("vgprs", "scratch", "occupancy", "static_lds")),
            "types": [one_type(ctx, n, u8, a.reps, a.warmup) for u8 in (False, True)]}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    bt.emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -16,10 +16,7 @@ One JSON line.
                               [--res real-time-software-defined-radio_amd/_build/rmeter.res]
 """
 import argparse
-import ctypes
-import json
 import math
-import os
 
 import numpy as np
 
@@ -40,12 +37,6 @@ def make_rows(S, n):
         row = (0.5 + 0.5 * (s + 1) / S) * base + 2 * math.pi * (50.0 * s) / FS + 1e-3 * rng.standard_normal(m)
         x[s] = np.tile(row.astype(np.float32), -(-n // m))[:n]
     return x
-
-
-def stats(ms):
-    ms = np.asarray(ms)
-    return {"best_us": round(float(ms.min()) * 1e3, 1), "median_us": round(float(np.median(ms)) * 1e3, 1),
-            "p90_us": round(float(np.percentile(ms, 90)) * 1e3, 1)}
 
 
 def verify(meter, model_args, x, ptr, stride, n):
@@ -81,10 +72,9 @@ def one_shape(ctx, name, S, n, window, reps, warmup):
             parts[k].append(v)
     meter.set_timing(False)
     nbytes = 4 * S * n
-    g = ctypes.c_double(0.0)
-    rtsdr._lib.check(ctx.lib.sdr_read_bandwidth(ctx.handle, nbytes, reps, ctypes.byref(g)), "sdr_read_bandwidth")
-    res.update({"call": stats(whole), "launches": {k: stats(v) for k, v in parts.items()}, "bytes": nbytes,
-                "read_probe_gbs": round(g.value, 1), "read_probe_us": round(nbytes / g.value / 1e3, 1)})
+    read = bt.read_gbs(ctx, nbytes, reps)
+    res.update({"call": bt.stats(whole, p90=True), "launches": {k: bt.stats(v, p90=True) for k, v in parts.items()}, "bytes": nbytes,
+                "read_probe_gbs": round(read, 1), "read_probe_us": round(nbytes / read / 1e3, 1)})
     res["reduce_gbs"] = round(nbytes / res["launches"]["reduce"]["best_us"] / 1e3, 1)
     res["reduce_over_read"] = round(res["launches"]["reduce"]["best_us"] / res["read_probe_us"], 3)
     res["call_over_read"] = round(res["call"]["best_us"] / res["read_probe_us"], 3)
@@ -107,12 +97,7 @@ def main():
                                           lambda m: m.group(1) + ("" if m.group(2) is None else "<seg>" if m.group(2) == "1" else "<chunks>"),
                                           ("vgprs", "scratch", "occupancy", "static_lds")),
            "shapes": [one_shape(ctx, name, S, n, a.window, a.reps, a.warmup) for name, S, n in SHAPES]}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    bt.emit(res, a.out)
 
 
 if __name__ == "__main__":
