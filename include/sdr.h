@@ -821,6 +821,83 @@ int  sdr_rmeter_state_dev(sdr_rmeter* rm, const sdr_rmeter_record** dev, const u
 int  sdr_rmeter_set_timing(sdr_rmeter* rm, int on);
 int  sdr_rmeter_stage_ms(sdr_rmeter* rm, float* ms);
 
+/* ---- cascade of second-order sections on rows of real samples ---------------------------------
+ * scipy.signal.sosfilt(sos, x, zi) per row in f64, rounded once to f32: the pilot notch, a sharp
+ * audio low-pass, a DC blocker, the K-weighting of ITU-R BS.1770 on a receiver's audio rows.  The
+ * reference has no such stage; the definition is rtsdr.sos_model (sosfilter.py).  sos: K rows of
+ * (b0, b1, b2, 1, a1, a2), 1 <= K <= SDR_SOS_MAX_SECTIONS; the state is scipy's zi / zf (direct form
+ * II transposed), [nrows][K][2] f64 on the device, carried from call to call until sdr_sos_reset.
+ * Three launches per call (csrc/sos.hip): the tiles of SDR_SOS_TILE samples from zero state
+ * (reduce), one wave per row that chains their end states (carry), every tile from its true state
+ * (apply); rows of one tile take the apply launch alone.  No atomics, no waiting between
+ * workgroups: the same calls give the same bits.  Every stride power of the recursion is formed on
+ * the host in long double and rounded once (a table per coefficient set, cached on the context).
+ * A NaN sample makes the rest of its row NaN, as scipy's loop does, and no other row.
+ * sdr_sos_process_dev: async; row s starts s x_stride floats into x and s y_stride into y; rows at
+ * any 4-byte alignment; the floats between rows are never touched; y == x filters in place; y ==
+ * NULL stores nothing and only advances the state.  sdr_sos_run: host rows stride floats apart
+ * (y_host may be NULL).  sdr_sos_state / _set_state synchronise.
+ * SDR_EINVAL (before any device work): NULL pointers, nrows outside 1 .. SDR_SOS_MAX_ROWS, K
+ * outside 1 .. SDR_SOS_MAX_SECTIONS, a non-finite coefficient, a0 != 1, a section with a pole on or
+ * outside the unit circle (|a2| >= 1 or |a1| >= 1 + a2), n outside [1, 2^31 - 1], a stride < n, a
+ * pointer not aligned to 4 B, y rows that overlap the x rows other than y == x with equal strides.
+ * No host fallback. */
+#define SDR_SOS_MAX_SECTIONS 4
+#define SDR_SOS_MAX_ROWS 4096
+#define SDR_SOS_TILE 2048
+typedef struct sdr_sos sdr_sos;
+int  sdr_sos_create(sdr_ctx* ctx, int nrows, const double* sos /* [K][6] */, int K, sdr_sos** out);
+void sdr_sos_destroy(sdr_sos* f);
+int  sdr_sos_reset(sdr_sos* f);                                                              /* async */
+int  sdr_sos_process_dev(sdr_sos* f, const float* x, int64_t x_stride, float* y, int64_t y_stride, int64_t n);   /* async */
+int  sdr_sos_run(sdr_sos* f, const float* x_host, float* y_host, int64_t stride, int64_t n); /* sync */
+int  sdr_sos_state(sdr_sos* f, double* host /* [nrows][K][2] */);                            /* synchronises */
+int  sdr_sos_set_state(sdr_sos* f, const double* host /* [nrows][K][2] */);                  /* synchronises */
+/* per-launch timing of the last call: reduce, carry, apply; ms: 3 floats (0 for a launch a short
+ * call skips).  Keep it off in measured loops. */
+int  sdr_sos_set_timing(sdr_sos* f, int on);
+int  sdr_sos_stage_ms(sdr_sos* f, float* ms);
+
+/* ---- programme loudness of audio rows (ITU-R BS.1770 K-weighting, segment energies) ----------
+ * Per stream and channel (1 or 2 rows of the same stride: ch0, ch1): the row through the two
+ * K-weighting sections at 48 kHz (the cascade above, state carried), times 1 / `reference` -- the
+ * row amplitude of PCM full scale, 2.0 for the output stage's x * 16384 -> int16 rule -- and the
+ * f64 sum of squares of every completed segment of `segment` samples of stream position; the open
+ * segment's partial sum and the position are carried.  The squares are of the f64 filter output,
+ * not of a row rounded to f32.  The definition is rtsdr.LoudnessModel; rtsdr.loudness_report turns
+ * the energies into momentary, short-term and gated integrated loudness (4 segments of 100 ms are
+ * a 400 ms gating block).  The cascade's three launches (its apply launch also leaves, per tile,
+ * the sums of squares on either side of the one segment boundary a tile can hold), then one wave
+ * per stream that folds them in a fixed order into the open segment and a ring of the latest `cap`
+ * completed segments.  sdr_loud_segments: the latest min(cap, completed) segment energies in
+ * order, row (s, ch) at host + (s channels + ch) cap, *first the stream index of the first of them,
+ * *count how many; synchronises.  sdr_loud_state_dev: the ring [nstreams][channels][cap] (segment g
+ * at g % cap) and the open sums [nstreams][channels], for a consumer on the stream.
+ * SDR_EINVAL (before any device work): NULL pointers (ch1 non-NULL with one channel, NULL with
+ * two), nstreams outside 1 .. SDR_SOS_MAX_ROWS, channels not 1 or 2, segment outside
+ * [SDR_LOUD_MIN_SEGMENT, SDR_LOUD_MAX_SEGMENT], cap outside [4, SDR_LOUD_MAX_CAP], a reference
+ * that is not finite and positive, n outside [1, 2^31 - 1], stride < n, a pointer not aligned to
+ * 4 B.  No host fallback. */
+#define SDR_LOUD_MIN_SEGMENT 2048
+#define SDR_LOUD_MAX_SEGMENT 16777216
+#define SDR_LOUD_MAX_CAP 1048576
+typedef struct sdr_loud_params {
+  int64_t segment;    /* samples of a segment (4800: 100 ms at 48 kHz) */
+  int cap;            /* completed segments kept per stream and channel */
+  double reference;   /* row amplitude of full scale */
+} sdr_loud_params;
+typedef struct sdr_loud sdr_loud;
+int  sdr_loud_create(sdr_ctx* ctx, int nstreams, int channels, const sdr_loud_params* params, sdr_loud** out);
+void sdr_loud_destroy(sdr_loud* l);
+int  sdr_loud_reset(sdr_loud* l);                                                            /* async */
+int  sdr_loud_process_dev(sdr_loud* l, const float* ch0, const float* ch1 /* NULL: mono */, int64_t stride, int64_t n);   /* async */
+int  sdr_loud_run(sdr_loud* l, const float* ch0_host, const float* ch1_host, int64_t stride, int64_t n);   /* sync */
+int  sdr_loud_segments(sdr_loud* l, double* host /* [nstreams][channels][cap] */, int64_t* first, int64_t* count);
+int  sdr_loud_state_dev(sdr_loud* l, const double** ring_dev, const double** open_dev);
+/* per-launch timing of the last call: reduce, carry, apply, fold; ms: 4 floats */
+int  sdr_loud_set_timing(sdr_loud* l, int on);
+int  sdr_loud_stage_ms(sdr_loud* l, float* ms);
+
 /* ---- spectral diagnostics -----------------------------------------
  * Bartlett PSD, model/fmSupportLib.py:66-140 (estimatePSD; the C++ src/fourier.cpp:36-110
  * advances sample and list positions by the same nfft/2 and is not the parity target):

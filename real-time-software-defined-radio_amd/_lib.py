@@ -38,6 +38,7 @@ SDR_RDS_CARRIER_NSTATE = 7
 SDR_IQC_NSTATE, SDR_IQC_CHUNK = 12, 4096   # the corrector of the capture (include/sdr.h sdr_iqc_*)
 SDR_INGEST_CHUNK = 4096                           # capture ingest (include/sdr.h sdr_ingest_*)
 SDR_RMETER_CHUNK, SDR_RMETER_SEG = 16384, 4096     # the rows' modulation meter (include/sdr.h sdr_rmeter_*)
+SDR_SOS_TILE, SDR_SOS_MAX_SECTIONS = 2048, 4       # cascades of second-order sections on rows (include/sdr.h sdr_sos_*)
 PLL_STATS = ("recurrences", "spec_r0", "spec_r1", "spec_r2", "sequential", "long_guessed", "long_chained",
              "long_maxgap", "long_stops", "long_tail", "long_linear")
 
@@ -152,6 +153,24 @@ SIGNATURES = {
     "sdr_rmeter_state_dev": (_i32, [_vp, _c.POINTER(_vp), _c.POINTER(_vp)]),
     "sdr_rmeter_set_timing": (_i32, [_vp, _i32]),
     "sdr_rmeter_stage_ms": (_i32, [_vp, _fp]),
+    "sdr_sos_create": (_i32, [_vp, _i32, _dp, _i32, _c.POINTER(_vp)]),
+    "sdr_sos_destroy": (None, [_vp]),
+    "sdr_sos_reset": (_i32, [_vp]),
+    "sdr_sos_process_dev": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64]),
+    "sdr_sos_run": (_i32, [_vp, _vp, _vp, _i64, _i64]),
+    "sdr_sos_state": (_i32, [_vp, _vp]),
+    "sdr_sos_set_state": (_i32, [_vp, _vp]),
+    "sdr_sos_set_timing": (_i32, [_vp, _i32]),
+    "sdr_sos_stage_ms": (_i32, [_vp, _fp]),
+    "sdr_loud_create": (_i32, [_vp, _i32, _i32, _vp, _c.POINTER(_vp)]),
+    "sdr_loud_destroy": (None, [_vp]),
+    "sdr_loud_reset": (_i32, [_vp]),
+    "sdr_loud_process_dev": (_i32, [_vp, _vp, _vp, _i64, _i64]),
+    "sdr_loud_run": (_i32, [_vp, _vp, _vp, _i64, _i64]),
+    "sdr_loud_segments": (_i32, [_vp, _vp, _c.POINTER(_i64), _c.POINTER(_i64)]),
+    "sdr_loud_state_dev": (_i32, [_vp, _c.POINTER(_vp), _c.POINTER(_vp)]),
+    "sdr_loud_set_timing": (_i32, [_vp, _i32]),
+    "sdr_loud_stage_ms": (_i32, [_vp, _fp]),
     "sdr_iqc_create": (_i32, [_vp, _i32, _vp, _c.POINTER(_vp)]),
     "sdr_iqc_destroy": (None, [_vp]),
     "sdr_iqc_reset": (_i32, [_vp]),

@@ -27,6 +27,7 @@ from . import capture
 from . import design
 from . import iqbalance
 from . import rowmeter
+from . import sosfilter
 from ._lib import RX_FILTERS, RX_OUTPUTS, SDR_IQ_F32, SDR_IQ_U8, SDR_RX_AUDIO, SDR_RX_RDS, SDR_RX_STEREO, check, f64p
 from .dsp import _taps
 
@@ -497,6 +498,27 @@ class Receiver(_Timed, _Handle):
         kw.setdefault("ctx", self.ctx)
         fs = design.AUDIO_FS * self._length(name) / self._length("demod")
         return RowMeter(self.S, int(round(window_s * fs)), nbins=nbins, scale=scale, limit=limit, **kw)
+
+
+    def audio_filter(self, sos, **kw) -> "RowSos":
+        """A RowSos (a cascade of second-order sections: design.pilot_notch_sos, an elliptic low-pass,
+        a DC blocker) sized to this receiver, one row per stream; per block
+        filt.process_rx(receiver, name) filters the rows of output `name` in place, or into out_ptr."""
+        kw.setdefault("ctx", self.ctx)
+        return RowSos(self.S, sos, **kw)
+
+    def loudness_meter(self, **kw) -> "LoudnessMeter":
+        """A LoudnessMeter sized to this receiver's 48 kHz audio rows: two channels on "left_de" /
+        "right_de" with stereo=True, else one on "audio_de"; "left" / "right" / "audio" where the
+        receiver has no de-emphasis.  Feed it with meter.process_rx(receiver) after a block and read
+        meter.report()."""
+        kw.setdefault("ctx", self.ctx)
+        return LoudnessMeter(self.S, channels=len(self.loudness_rows()), **kw)
+
+    def loudness_rows(self) -> tuple:
+        """The outputs a loudness meter of this receiver reads (LoudnessMeter.process_rx's default)."""
+        names = ("left", "right") if self.flags & SDR_RX_STEREO else ("audio",)
+        return tuple(n + "_de" for n in names) if self._produces(RX_OUTPUTS.index(names[0] + "_de")) else names
 
 
 class MonoBlockProcessor:
@@ -1635,6 +1657,164 @@ class RowMeter(_Timed, _LazyHandle):
 
     def reset(self):
         """Zero the records, the histogram and the stream position (async)."""
+        self._do("reset")
+
+
+class RowSos(_Timed, _LazyHandle):
+    """A cascade of 1 .. 4 second-order sections on `nrows` rows of real float32 samples on the GPU
+    (sdr_sos, csrc/sos.hip): scipy.signal.sosfilt(sos, x, zi) per row in float64, rounded once to
+    float32, the state (scipy's zi / zf, [nrows, K, 2] float64) carried on the device from call to
+    call.  sos: [K, 6] with a0 == 1 and every pole inside the unit circle (design.pilot_notch_sos,
+    design.k_weighting_sos, scipy.signal.ellip / butter(..., output="sos")).  Three launches per
+    call, one for rows of up to 2048 samples; the same calls give the same bits.  The rule is
+    rtsdr.sos_model.  The arguments are checked before a context exists; the device object is made
+    at the first call that needs it."""
+
+    TILE, MAX_SECTIONS = _lib.SDR_SOS_TILE, _lib.SDR_SOS_MAX_SECTIONS
+    MAX_N = sosfilter.MAX_N
+    _prefix = "sdr_sos"
+    _STAGES = ("reduce", "carry", "apply")                        # stage_ms: the last call's launches
+
+    def __init__(self, nrows: int, sos, ctx=None):
+        self.nrows, self.sos = sosfilter.check_rows_count(nrows), sosfilter.check_sos(sos)
+        self.K = self.sos.shape[0]
+        self._ctx = ctx
+
+    def _create_args(self):
+        return self.nrows, f64p(self.sos), self.K
+
+    def process_dev(self, x_ptr: int, x_stride: int, y_ptr: int, y_stride: int, n: int):
+        """n samples per row at device pointer x_ptr, rows x_stride floats apart, to y_ptr (y_stride
+        apart): any 4-byte alignment, the floats between rows are never touched; y_ptr == x_ptr
+        filters in place; y_ptr 0 / None stores nothing and only advances the state.  Async on the
+        context stream."""
+        x_ptr, y_ptr, x_stride, y_stride, n = int(x_ptr or 0), int(y_ptr or 0), int(x_stride), int(y_stride), int(n)
+        if not x_ptr:
+            raise ValueError("x_ptr is NULL")
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError(f"n={n} outside [1, 2^31 - 1]")
+        if x_stride < n or (y_ptr and y_stride < n):
+            raise ValueError(f"stride ({x_stride}, {y_stride}) < n={n}")
+        if x_ptr % 4 or y_ptr % 4:
+            raise ValueError("x_ptr and y_ptr must be aligned to 4 B")
+        self._do("process_dev", x_ptr, x_stride, y_ptr or None, y_stride, n)
+
+    def process_rx(self, receiver: "Receiver", name: str, out_ptr=None):
+        """The receiver's latest rows of output `name` (looked up at every call), filtered in place,
+        or into out_ptr -- rows the same stride apart -- which leaves the receiver's rows as they are."""
+        if receiver.S != self.nrows:
+            raise ValueError(f"the receiver has {receiver.S} streams, the filter {self.nrows} rows")
+        ptr, stride, n = receiver.output_ptr(name)
+        self.process_dev(ptr, stride, ptr if out_ptr is None else out_ptr, stride, n)
+
+    def run(self, rows_host) -> np.ndarray:
+        """(nrows, n) real samples from the host to float32 (nrows, n); synchronous (sdr_sos_run)."""
+        x = np.ascontiguousarray(sosfilter.as_rows(rows_host, self.nrows))
+        y = np.empty_like(x)
+        self._do("run", x.ctypes.data, y.ctypes.data, x.shape[1], x.shape[1])
+        return y
+
+    def state(self) -> np.ndarray:
+        """float64 [nrows, K, 2]: scipy's zf after the latest call (sdr_sos_state; synchronises)."""
+        z = np.empty((self.nrows, self.K, 2))
+        self._do("state", z.ctypes.data)
+        return z
+
+    def set_state(self, z):
+        """The state the next call starts from: float64 [nrows, K, 2], scipy's zi (synchronises)."""
+        z = np.ascontiguousarray(z, dtype=np.float64)
+        if z.shape != (self.nrows, self.K, 2):
+            raise ValueError(f"state must be ({self.nrows}, {self.K}, 2), not {z.shape}")
+        self._do("set_state", z.ctypes.data)
+
+    def reset(self):
+        """Zero state (async)."""
+        self._do("reset")
+
+
+class _LoudParamsC(ctypes.Structure):                            # include/sdr.h sdr_loud_params
+    _fields_ = [("segment", ctypes.c_int64), ("cap", ctypes.c_int), ("reference", ctypes.c_double)]
+
+
+class LoudnessMeter(_Timed, _LazyHandle):
+    """Programme loudness of `nstreams` audio streams of 1 or 2 channels on the GPU (sdr_loud,
+    csrc/sos.hip), read from a Receiver's 48 kHz audio rows where it left them: every row through
+    the two K-weighting sections of ITU-R BS.1770 with carried state, divided by `reference` (the row
+    amplitude of PCM full scale: the output stage writes int16(x * 16384), so 2.0), and the float64
+    sum of squares of every completed segment of `segment` samples (4800: 100 ms) of stream
+    position, the latest `cap` of them kept per stream and channel.  Four launches per call, nothing
+    returns to the host until segments() or report() is asked.  The rule is rtsdr.LoudnessModel;
+    report() is rtsdr.loudness_report of the kept segments: momentary, short-term and gated
+    integrated loudness in LUFS (the default cap holds 409.6 s).  The arguments are checked before
+    a context exists."""
+
+    MAX_N = sosfilter.MAX_N
+    _prefix = "sdr_loud"
+    _STAGES = ("reduce", "carry", "apply", "fold")
+
+    def __init__(self, nstreams: int, channels: int = 2, segment: int = 4800, cap: int = 4096, reference: float = 2.0, ctx=None):
+        self.nstreams, self.channels, self.segment, self.cap, self.reference = sosfilter.check_loudness_params(nstreams, channels, segment, cap,
+                                                                                                              reference)
+        self._ctx = ctx
+
+    def _create_args(self):
+        return self.nstreams, self.channels, ctypes.byref(_LoudParamsC(self.segment, self.cap, self.reference))
+
+    def process_dev(self, ch0_ptr: int, ch1_ptr: int, stride: int, n: int):
+        """n samples per row of each channel at device pointers ch0_ptr and ch1_ptr (0 / None with one
+        channel), rows stride floats apart, any 4-byte alignment; async on the context stream."""
+        p0, p1, stride, n = int(ch0_ptr or 0), int(ch1_ptr or 0), int(stride), int(n)
+        if not p0 or bool(p1) != (self.channels == 2):
+            raise ValueError(f"{self.channels} channel(s): ch0_ptr must be given, ch1_ptr with two channels only")
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError(f"n={n} outside [1, 2^31 - 1]")
+        if stride < n:
+            raise ValueError(f"stride={stride} < n={n}")
+        if p0 % 4 or p1 % 4:
+            raise ValueError("the row pointers must be aligned to 4 B")
+        self._do("process_dev", p0, p1 or None, stride, n)
+
+    def process_rx(self, receiver: "Receiver", names=None):
+        """The receiver's latest rows of the outputs `names`, one per channel, read in place (None:
+        receiver.loudness_rows(), ("left_de", "right_de") of a stereo receiver with de-emphasis)."""
+        if receiver.S != self.nstreams:
+            raise ValueError(f"the receiver has {receiver.S} streams, the meter {self.nstreams}")
+        names = receiver.loudness_rows() if names is None else tuple(names)
+        if len(names) != self.channels:
+            raise ValueError(f"{len(names)} outputs for {self.channels} channel(s)")
+        rows = [receiver.output_ptr(k) for k in names]
+        if any(r[1:] != rows[0][1:] for r in rows):
+            raise ValueError("the channels' rows differ in stride or length")
+        self.process_dev(rows[0][0], rows[1][0] if self.channels == 2 else None, rows[0][1], rows[0][2])
+
+    def run(self, rows_host):
+        """A list of `channels` arrays (nstreams, n) from the host; synchronous (sdr_loud_run)."""
+        if len(rows_host) != self.channels:
+            raise ValueError(f"{len(rows_host)} row sets for {self.channels} channel(s)")
+        xs = [np.ascontiguousarray(sosfilter.as_rows(r, self.nstreams)) for r in rows_host]
+        if any(x.shape != xs[0].shape for x in xs):
+            raise ValueError("the channels' rows differ in length")
+        self._do("run", xs[0].ctypes.data, xs[1].ctypes.data if self.channels == 2 else None, xs[0].shape[1], xs[0].shape[1])
+
+    def segments(self):
+        """(first, energies): float64 [nstreams, channels, count], the latest min(cap, completed)
+        segment energies in order, and the stream index of the first (sdr_loud_segments; synchronises)."""
+        buf = np.empty((self.nstreams, self.channels, self.cap))
+        first, count = ctypes.c_int64(), ctypes.c_int64()
+        self._do("segments", buf.ctypes.data, ctypes.byref(first), ctypes.byref(count))
+        return first.value, np.ascontiguousarray(buf[:, :, :count.value])
+
+    def report(self) -> "sosfilter.LoudnessReport":
+        """rtsdr.loudness_report of the kept segments (a segment must be 100 ms of 48 kHz: 4800)."""
+        return sosfilter.loudness_report(self.segments()[1], self.segment)
+
+    def state_ptr(self):
+        """(ring pointer, open pointer): the device arrays float64 [nstreams][channels][cap] (segment g
+        at g % cap) and [nstreams][channels] (sdr_loud_state_dev)."""
+        return self._ptr_out("state_dev", 2)
+
+    def reset(self):
+        """Zero the filter states, the segments and the stream position (async)."""
         self._do("reset")
 
 

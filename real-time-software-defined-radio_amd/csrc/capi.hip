@@ -314,6 +314,7 @@ void sdr_destroy(sdr_ctx* c) {
   for (PllTable& t : c->resp) (void)hipFree(t.dev);
   for (PllTable& t : c->qtab) (void)hipFree(t.dev);
   for (IirTab& t : c->iir) (void)hipFree(t.dev);
+  for (SosTab& t : c->sos) (void)hipFree(t.dev);
   if (c->pll_stats) (void)hipFree(c->pll_stats);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;

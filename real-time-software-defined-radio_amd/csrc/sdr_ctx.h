@@ -46,6 +46,13 @@ struct IirTab {
   double* dev = nullptr;
 };
 
+// a second-order cascade's power tables on the device (sos.hip sos_table), per coefficient set
+struct SosTab {
+  int K = 0;
+  double sos[SDR_SOS_MAX_SECTIONS * 6] = {};
+  double* dev = nullptr;
+};
+
 // the calling thread's last error message; returns `code`
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
@@ -65,6 +72,8 @@ struct sdr_ctx {
   std::list<sdrint::PllTable> resp, qtab;
   // pole-power tables of the first-order sections run on the context (a few; never evicted)
   std::list<sdrint::IirTab> iir;
+  // power tables of the second-order cascades made on the context (a few; never evicted)
+  std::list<sdrint::SosTab> sos;
   // PLL solve counters (SDR_PLL_NSTATS, device; sdr_pll_stats): every PLL launch of the
   // context and of its receivers adds to them
   unsigned long long* pll_stats = nullptr;

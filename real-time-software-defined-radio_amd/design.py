@@ -190,3 +190,19 @@ def spectrum_window(window, nfft: int) -> np.ndarray:
     if np.sum(w) == 0.0:
         raise ValueError("the window sums to zero")
     return w
+
+
+def k_weighting_sos(fs: float = 48e3) -> np.ndarray:
+    """The two K-weighting sections of ITU-R BS.1770-4 (tables 1 and 2) as sos [2, 6]: the
+    pre-filter (a high shelf for the head's acoustics) and the RLB high-pass.  The standard
+    tabulates 48 kHz only, and the receiver's audio rows are 48 kHz: any other rate is refused."""
+    if fs != 48e3:
+        raise ValueError(f"K-weighting is tabulated at 48 kHz only, not fs={fs}")
+    return np.array([[1.53512485958697, -2.69169618940638, 1.19839281085285, 1.0, -1.69065929318241, 0.73248077421585],
+                     [1.0, -2.0, 1.0, 1.0, -1.99004745483398, 0.99007225036621]])
+
+
+def pilot_notch_sos(fs: float = 48e3, f0: float = PILOT_FREQ, q: float = 30.0) -> np.ndarray:
+    """A notch at the 19 kHz pilot for the audio rows: signal.tf2sos(*signal.iirnotch(f0, q, fs)),
+    one section, -3 dB width f0 / q."""
+    return signal.tf2sos(*signal.iirnotch(f0, q, fs))

@@ -1,5 +1,5 @@
 """What the blocks' timing tools share (ddc_time, pfb_time, rsmp_time, spectrum_time, rspec_time,
-iqc_time, ingest_time, rmeter_time, blend_time, rds_link_time, rds_sync_time, rds_clock_time,
+iqc_time, ingest_time, rmeter_time, sos_time, blend_time, rds_link_time, rds_sync_time, rds_clock_time,
 rds_carrier_time): the HIP-event loop, best and median (and p90) of its repeats, the parser of a
 build's kernel resource remarks, the copy and read bandwidth of the box and the way a result
 leaves as one JSON line."""
