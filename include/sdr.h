@@ -414,7 +414,13 @@ int sdr_rx_set_depth(sdr_rx* rx, int depth);
  * processed).  sdr_rx_process_dev then does NOT order the front half after earlier work on
  * the context stream: its IQ must be ready when it is called (device-resident data, or an
  * upload that has been waited for).  The back half and everything after it on the context
- * stream see block k complete, as without pipelining. */
+ * stream see block k complete, as without pipelining.
+ * Readers of the rows: work enqueued on the context stream between sdr_rx_process_dev(k) and
+ * sdr_rx_process_dev(k+1) sees block k's rows, every one of them, however far the host runs
+ * ahead of the GPU -- the call for block k+1 orders the launches that will overwrite the row
+ * set (block k+nq's front half and PLLs, nq = 2 or 3 row sets) after it.  Work enqueued later
+ * than that call, or on another stream, has no such guarantee: wait for the context stream
+ * before block k+nq is processed. */
 int sdr_rx_set_pipeline(sdr_rx* rx, int on);
 int sdr_rx_output(sdr_rx* rx, int which, float** dev, int64_t* stride, int64_t* n);
 int sdr_rx_fetch(sdr_rx* rx, int which, float* host, int64_t host_stride); /* sync, all streams */

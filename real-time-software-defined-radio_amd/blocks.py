@@ -391,7 +391,9 @@ class Receiver(_Timed, _Handle):
 
     def process_dev(self, iq_ptr: int, iq_stride: int):
         """One block from device memory (async on the context stream); outputs stay on the
-        GPU (output_ptr)."""
+        GPU (output_ptr).  What is enqueued on the context stream before the next process_dev call
+        (a stage's process_rx) sees this block's rows, also behind a pipelined receiver that the
+        host runs blocks ahead of; later work must be waited for before the row set comes round."""
         check(self.lib.sdr_rx_process_dev(self.handle, iq_ptr, int(iq_stride)), "sdr_rx_process_dev")
 
     def output_ptr(self, name: str):
@@ -726,7 +728,8 @@ class RdsLinkBank(_RdsBank):
 
     def process_rx(self, receiver: "Receiver"):
         """The receiver's latest "rrc_i" rows (looked up at every call: a pipelined receiver
-        alternates its row sets)."""
+        alternates its row sets; call it before the receiver's next process_dev, which keeps the
+        rows until this call has read them)."""
         self.process_dev(*self._receiver_rows(receiver, "rrc_i"))
 
     def events(self):
@@ -844,7 +847,8 @@ class RdsClockBank(_RdsBank):
 
     def process_rx(self, receiver: "Receiver"):
         """The receiver's latest "rrc_i" rows (looked up at every call: a pipelined receiver
-        alternates its row sets)."""
+        alternates its row sets; call it before the receiver's next process_dev, which keeps the
+        rows until this call has read them)."""
         self.process_dev(*self._receiver_rows(receiver, "rrc_i"))
 
     def bits(self):
@@ -909,7 +913,8 @@ class RdsCarrierBank(_RdsBank):
 
     def process_rx(self, receiver: "Receiver"):
         """The receiver's latest "rrc_i" and "rrc_q" rows (looked up at every call: a pipelined
-        receiver alternates its row sets)."""
+        receiver alternates its row sets; call it before the receiver's next process_dev, which
+        keeps the rows until this call has read them)."""
         self.process_dev(*self._receiver_rows(receiver, "rrc_i", "rrc_q"))
 
     def rows(self) -> np.ndarray:
@@ -1500,7 +1505,8 @@ class RowSpectrum(Spectrum):
 
     def process_rx(self, receiver: "Receiver", out_ptr: int, name: str = "demod", out_stride=None) -> int:
         """The receiver's latest rows of output `name` (looked up at every call: a pipelined
-        receiver alternates its row sets) -> out_ptr as process_dev.  Returns rows."""
+        receiver alternates its row sets; call it before the receiver's next process_dev, which
+        keeps the rows until this call has read them) -> out_ptr as process_dev.  Returns rows."""
         if receiver.S != self.nrows:
             raise ValueError(f"the receiver has {receiver.S} streams, the spectrum {self.nrows} rows")
         ptr, stride, n = receiver.output_ptr(name)
@@ -1617,7 +1623,8 @@ class RowMeter(_Timed, _LazyHandle):
 
     def process_rx(self, receiver: "Receiver", name: str = "demod"):
         """The receiver's latest rows of output `name`, read in place (looked up at every call: a
-        pipelined receiver alternates its row sets)."""
+        pipelined receiver alternates its row sets; call it before the receiver's next process_dev,
+        which keeps the rows until this call has read them)."""
         if receiver.S != self.nstreams:
             raise ValueError(f"the receiver has {receiver.S} streams, the meter {self.nstreams}")
         ptr, stride, n = receiver.output_ptr(name)
@@ -1701,7 +1708,8 @@ class RowSos(_Timed, _LazyHandle):
 
     def process_rx(self, receiver: "Receiver", name: str, out_ptr=None):
         """The receiver's latest rows of output `name` (looked up at every call), filtered in place,
-        or into out_ptr -- rows the same stride apart -- which leaves the receiver's rows as they are."""
+        or into out_ptr -- rows the same stride apart -- which leaves the receiver's rows as they are.
+        Call it before the receiver's next process_dev, which keeps the rows until this call is done."""
         if receiver.S != self.nrows:
             raise ValueError(f"the receiver has {receiver.S} streams, the filter {self.nrows} rows")
         ptr, stride, n = receiver.output_ptr(name)
@@ -1776,7 +1784,8 @@ class LoudnessMeter(_Timed, _LazyHandle):
 
     def process_rx(self, receiver: "Receiver", names=None):
         """The receiver's latest rows of the outputs `names`, one per channel, read in place (None:
-        receiver.loudness_rows(), ("left_de", "right_de") of a stereo receiver with de-emphasis)."""
+        receiver.loudness_rows(), ("left_de", "right_de") of a stereo receiver with de-emphasis).  Call
+        it before the receiver's next process_dev, which keeps the rows until this call has read them."""
         if receiver.S != self.nstreams:
             raise ValueError(f"the receiver has {receiver.S} streams, the meter {self.nstreams}")
         names = receiver.loudness_rows() if names is None else tuple(names)

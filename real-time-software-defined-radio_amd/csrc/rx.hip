@@ -78,6 +78,7 @@ struct sdr_rx : RxLayout {             // M, A, R, the rows' lengths and strides
   hipStream_t front = nullptr;          // FE, stages A and B
   hipStream_t mid = nullptr;            // the PLLs (prep, lanes, NCO)
   hipEvent_t ev_front[3] = {}, ev_mid[3] = {}, ev_back[3] = {}, ev_done[4] = {};
+  hipEvent_t ev_read[3] = {};           // row set q's readers on the context stream (recorded by the next sdr_rx_process_dev)
   // sdr_rx_submit: depth blocks in flight before a submit waits (sdr_rx_set_depth); pinned
   // slots (input and outputs) per block, depth + 1 of them; the blocks in flight, oldest first
   int depth = 1; int64_t subs = 0;
@@ -251,7 +252,7 @@ void sdr_rx_destroy(sdr_rx* r) {
   for (void* p : {r->pin_in, (void*)r->pin_out})
     if (p) (void)hipHostFree(p);
   auto drop = [](auto& evs) { for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e); };
-  drop(r->ev_front); drop(r->ev_mid); drop(r->ev_back); drop(r->ev_done);
+  drop(r->ev_front); drop(r->ev_mid); drop(r->ev_back); drop(r->ev_read); drop(r->ev_done);
   if (r->front) (void)hipStreamDestroy(r->front);
   if (r->mid) (void)hipStreamDestroy(r->mid);
   delete r;
@@ -373,7 +374,7 @@ int sdr_rx_set_pipeline(sdr_rx* r, int on) {
     HIP_TRY(hipStreamCreateWithFlags(&r->front, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&r->mid, hipStreamNonBlocking));
     for (int q = 0; q < 3; ++q)
-      for (hipEvent_t* e : {&r->ev_front[q], &r->ev_mid[q], &r->ev_back[q]}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+      for (hipEvent_t* e : {&r->ev_front[q], &r->ev_mid[q], &r->ev_back[q], &r->ev_read[q]}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
   }
   r->pipe = on != 0;
   return SDR_OK;
@@ -454,7 +455,10 @@ int rx_front(RxBlock& b, const void* iq, int64_t xs, bool fast) {
     // states of block k-1 (r04b: not when its front half ran on this same stream, in order)
     if (r->blocks >= 1 && r->last_fs != fs) HIP_TRY(hipStreamWaitEvent(fs, r->ev_front[(b.q + r->nq - 1) % r->nq], 0));
     r->last_fs = fs;
-    if (set_busy(r)) HIP_TRY(hipStreamWaitEvent(fs, r->ev_back[b.q], 0));
+    if (set_busy(r)) {
+      HIP_TRY(hipStreamWaitEvent(fs, r->ev_back[b.q], 0));
+      HIP_TRY(hipStreamWaitEvent(fs, r->ev_read[b.q], 0));
+    }
   }
   HIP_TRY(mark(r, 0, fs));
   // FE: RF FIR + decimate + demod (fe.hip).  The tiled kernels take the reference's RF
@@ -571,7 +575,10 @@ int rx_pll(RxBlock& b) {
     HIP_TRY(hipEventRecord(r->ev_front[q], b.fs));
     if (plls) {
       HIP_TRY(hipStreamWaitEvent(ps, r->ev_front[q], 0));
-      if (set_busy(r)) HIP_TRY(hipStreamWaitEvent(ps, r->ev_back[q], 0));
+      if (set_busy(r)) {
+        HIP_TRY(hipStreamWaitEvent(ps, r->ev_back[q], 0));
+        HIP_TRY(hipStreamWaitEvent(ps, r->ev_read[q], 0));
+      }
     } else {
       HIP_TRY(hipStreamWaitEvent(b.st, r->ev_front[q], 0));
     }
@@ -709,6 +716,14 @@ int sdr_rx_process_dev(sdr_rx* r, const void* iq, int64_t iq_stride) {
   const bool fast = (Trf == 101 || Trf == 151) && r->rf_decim == 10 && (r->S <= 1 || r->u8 || xs % (r->u8 ? 8 : 2) == 0) &&
                     ((uintptr_t)iq % (r->u8 ? 4 : 16)) == 0;
   b.st = r->c->stream; b.fs = (r->pipe && fast) ? r->front : b.st;
+  // Whatever the caller put on the context stream since block k-1 (readers of its rows: the RDS
+  // banks, meters, spectra, filters in place) belongs to block k-1's row set: ev_read of that set
+  // is recorded behind it, and the front half and the PLLs of block k-1+nq wait for it beside
+  // ev_back before they overwrite the set -- the readers come first however far the host runs
+  // ahead.  Block k's own front half waits for block k-nq's events only and still overlaps.  An
+  // event of its own: ev_back is also a submitted block's completion (sdr_rx_submit), and recorded
+  // again here the host's wait for block k-1 ended late (c4 1 290 -> 760 - 1 050 MS/s).
+  if (r->pipe && r->blocks >= 1) HIP_TRY(hipEventRecord(r->ev_read[(b.q + r->nq - 1) % r->nq], b.st));
   for (int f = 0; f < SDR_RX_NFILTERS; ++f)
     if (filter_used(r, f)) TRY(get_taps(r->c, r->taps[f].data(), (int)r->taps[f].size(), &b.ts[f]));
   b.ms = r->out_stride[SDR_RX_O_DEMOD];
