@@ -904,6 +904,68 @@ int  sdr_loud_state_dev(sdr_loud* l, const double** ring_dev, const double** ope
 int  sdr_loud_set_timing(sdr_loud* l, int on);
 int  sdr_loud_stage_ms(sdr_loud* l, float* ms);
 
+/* ---- true peak of audio rows (ITU-R BS.1770 annex 2: a polyphase interpolator, maxima only) ---
+ * Per stream and channel (1 or 2 rows of the same stride: ch0, ch1) and per input sample at stream
+ * position t (samples since the last reset, x[t] = 0 for t < 0) the `up` interpolated values
+ *   y[t][p] = sum_{k = 0 .. taps - 1} f64(h[p][k]) f64(x[t - k]),   f64, from 0.0, k ascending
+ * (an f32 x f32 product is exact in f64: fused or not, the same bits), of which only maxima are
+ * kept: m[t] = max_p |y[t][p]| over the finite y (0.0 if none) and the sample peak q[t] = |x[t]|
+ * (0.0 if x[t] is not finite).  A non-finite y counts in `nonfinite` and enters no maximum.  The
+ * stream is cut into segments of `segment` samples of position; a segment's true peak is max m[t]
+ * and its sample peak max q[t] over its samples.  The open segment's maxima, the position and the
+ * last taps - 1 samples are carried from call to call on the device.  h = NULL: the 48-tap, 4-phase
+ * table of BS.1770-4 annex 2 (up = 4, taps = 12; rtsdr.design.true_peak_fir), for 48 kHz rows.  The
+ * definition is rtsdr.TruePeakModel, which the device equals bit for bit; rtsdr.true_peak_report
+ * turns maxima into dBTP (the row amplitude of full scale is 2.0, as for sdr_loud).
+ * Two launches per call (csrc/tpeak.hip): one workgroup per piece of a segment -- the pieces are
+ * cut at the segment boundaries from the position the host carries -- forms the values in
+ * registers and leaves one record; one wave per (stream, channel) folds the records into the open
+ * segment, the ring of the latest `cap` completed segments (segment g at g % cap), the call's and
+ * the totals' record, and stores the new history.  No atomics: the same calls give the same bits.
+ * sdr_tpeak_process_dev: async; row (s, ch) starts s stride floats into ch0 / ch1; rows at any
+ * 4-byte alignment; the stride - n floats between rows are never read; 1 <= n <= 2^31 - 1; all
+ * offsets are 64-bit.  It may grow the object's work array, which waits for the stream once.
+ * sdr_tpeak_run: host rows stride floats apart.  sdr_tpeak_records and _segments synchronise.
+ * sdr_tpeak_segments: the latest min(cap, completed) segments' true and sample peaks in order, row
+ * (s, ch) at host + (s channels + ch) cap, *first the stream index of the first of them, *count how
+ * many.  sdr_tpeak_state_dev: the two rings [nstreams][channels][cap] and the records
+ * [nstreams][channels], for a consumer on the stream.
+ * SDR_EINVAL (before any device work): NULL pointers (ch1 non-NULL with one channel, NULL with
+ * two), nstreams outside 1 .. SDR_SOS_MAX_ROWS, channels not 1 or 2, up outside 1 ..
+ * SDR_TPEAK_MAX_UP, taps outside 1 .. SDR_TPEAK_MAX_TAPS (h = NULL: up and taps other than 4 and 12
+ * or both 0), a non-finite coefficient, segment outside [SDR_LOUD_MIN_SEGMENT,
+ * SDR_LOUD_MAX_SEGMENT], cap outside [4, SDR_LOUD_MAX_CAP], n outside [1, 2^31 - 1], stride < n, a
+ * pointer not aligned to 4 B.  No host fallback. */
+#define SDR_TPEAK_MAX_UP 8
+#define SDR_TPEAK_MAX_TAPS 32
+typedef struct sdr_tpeak_params {
+  int up, taps;       /* phases, and taps of a phase */
+  const float* h;     /* [up][taps]; NULL: BS.1770-4 annex 2, 4 x 12 */
+  int64_t segment;    /* samples of a segment (4800: 100 ms at 48 kHz) */
+  int cap;            /* completed segments kept per stream and channel */
+} sdr_tpeak_params;
+typedef struct sdr_tpeak_record {
+  int64_t n, nonfinite;                                                   /* the latest call */
+  double peak, sample_peak;
+  int64_t calls, total_n, total_nonfinite;                                /* since the last reset */
+  double total_peak, total_sample_peak;
+  int64_t segments;                                                       /* completed since the last reset */
+  double open_peak, open_sample_peak;                                     /* the unfinished segment */
+} sdr_tpeak_record;
+typedef struct sdr_tpeak sdr_tpeak;
+int  sdr_tpeak_create(sdr_ctx* ctx, int nstreams, int channels, const sdr_tpeak_params* params, sdr_tpeak** out);
+void sdr_tpeak_destroy(sdr_tpeak* tp);
+int  sdr_tpeak_reset(sdr_tpeak* tp);                                                         /* async */
+int  sdr_tpeak_process_dev(sdr_tpeak* tp, const float* ch0, const float* ch1 /* NULL: mono */, int64_t stride, int64_t n);   /* async */
+int  sdr_tpeak_run(sdr_tpeak* tp, const float* ch0_host, const float* ch1_host, int64_t stride, int64_t n);   /* sync */
+int  sdr_tpeak_records(sdr_tpeak* tp, sdr_tpeak_record* host /* [nstreams][channels] */);    /* synchronises */
+int  sdr_tpeak_segments(sdr_tpeak* tp, double* peaks_host, double* sample_peaks_host /* [nstreams][channels][cap] */, int64_t* first,
+                        int64_t* count);
+int  sdr_tpeak_state_dev(sdr_tpeak* tp, const double** peaks_dev, const double** sample_peaks_dev, const sdr_tpeak_record** records_dev);
+/* per-launch timing of the last call: reduce, fold; ms: 2 floats.  Keep it off in measured loops. */
+int  sdr_tpeak_set_timing(sdr_tpeak* tp, int on);
+int  sdr_tpeak_stage_ms(sdr_tpeak* tp, float* ms);
+
 /* ---- spectral diagnostics -----------------------------------------
  * Bartlett PSD, model/fmSupportLib.py:66-140 (estimatePSD; the C++ src/fourier.cpp:36-110
  * advances sample and list positions by the same nfft/2 and is not the parity target):

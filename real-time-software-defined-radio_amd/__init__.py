@@ -39,7 +39,10 @@ numpy: the specification) and RowMeter (device, Receiver.modulation_meter, Recei
 and on the audio rows, cascades of second-order sections (pilot notch, elliptic low-pass, DC
 blocker, K-weighting) and the programme loudness of ITU-R BS.1770 built on them: sos_model,
 LoudnessModel, loudness_report (host, numpy / scipy: the specification), RowSos
-(Receiver.audio_filter) and LoudnessMeter (device, Receiver.loudness_meter).
+(Receiver.audio_filter) and LoudnessMeter (device, Receiver.loudness_meter); beside it the other two
+figures of a broadcast monitor, the true peak of BS.1770 annex 2 and the loudness range of EBU Tech
+3342: TruePeakModel, true_peak_report, loudness_range (host, numpy: the specification) and
+TruePeakMeter (device, Receiver.true_peak_meter).
 See DESIGN.md and INTEGRATION.md.
 """
 from . import design, synth  # noqa: F401
@@ -47,7 +50,7 @@ from ._lib import (SDR_IQ_F32, SDR_IQ_S8, SDR_IQ_S16, SDR_IQ_U8, SDR_PRE_MIX, SD
                    DeviceBuffer, SdrError, SdrUnavailable, Timer, device_count, device_info, get_context,
                    load_library)
 from .blocks import (BlendControl, BlendParams, BlendState, CaptureIngest, Channelizer, FilterBank, IqCorrector, LoudnessMeter, MonoBlockProcessor, MpxQuality, RdsBlockProcessor, RdsCarrierBank, RdsClockBank, RdsLinkBank, RdsLinkLayer, RdsSyncBank,  # noqa: F401
-                     Receiver, RowMeter, RowResampler, RowSos, RowSpectrum, Spectrum, StereoBlockProcessor, find_channels, mpx_quality, rds_groups,
+                     Receiver, RowMeter, RowResampler, RowSos, RowSpectrum, Spectrum, StereoBlockProcessor, TruePeakMeter, find_channels, mpx_quality, rds_groups,
                      spectrum_rows)
 from .rdssync import RdsBlockSync, RdsProgramme  # noqa: F401
 from .rdsclock import RdsSymbolClock  # noqa: F401
@@ -56,6 +59,7 @@ from .iqbalance import IqBalance, IqState  # noqa: F401
 from .capture import IngestMeter, capture_format, ingest_model  # noqa: F401
 from .rowmeter import ModulationReport, MpxLevels, RowMeterModel, RowMeterRecord, modulation_report, mpx_levels, row_meter_model  # noqa: F401
 from .sosfilter import LoudnessModel, LoudnessReport, loudness_report, sos_model  # noqa: F401
+from .truepeak import LoudnessRange, TruePeakModel, TruePeakRecord, TruePeakReport, loudness_range, true_peak_report  # noqa: F401
 from .design import impulseResponseRootRaisedCosine, my_filterImpulseResponse  # noqa: F401
 from .dsp import (DFT, MonoState, estimatePSD, fm_mono_range, fm_mono_streams, split_halo, fmDemodArctan, fmPll, lfilter, lfilter_decim,  # noqa: F401
                   audio_blend_dev, audio_out, deemphasis, iir1, mono_block, my_convoloution, resample, rf_frontend_block)

@@ -171,6 +171,16 @@ SIGNATURES = {
     "sdr_loud_state_dev": (_i32, [_vp, _c.POINTER(_vp), _c.POINTER(_vp)]),
     "sdr_loud_set_timing": (_i32, [_vp, _i32]),
     "sdr_loud_stage_ms": (_i32, [_vp, _fp]),
+    "sdr_tpeak_create": (_i32, [_vp, _i32, _i32, _vp, _c.POINTER(_vp)]),
+    "sdr_tpeak_destroy": (None, [_vp]),
+    "sdr_tpeak_reset": (_i32, [_vp]),
+    "sdr_tpeak_process_dev": (_i32, [_vp, _vp, _vp, _i64, _i64]),
+    "sdr_tpeak_run": (_i32, [_vp, _vp, _vp, _i64, _i64]),
+    "sdr_tpeak_records": (_i32, [_vp, _vp]),
+    "sdr_tpeak_segments": (_i32, [_vp, _vp, _vp, _c.POINTER(_i64), _c.POINTER(_i64)]),
+    "sdr_tpeak_state_dev": (_i32, [_vp, _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp)]),
+    "sdr_tpeak_set_timing": (_i32, [_vp, _i32]),
+    "sdr_tpeak_stage_ms": (_i32, [_vp, _fp]),
     "sdr_iqc_create": (_i32, [_vp, _i32, _vp, _c.POINTER(_vp)]),
     "sdr_iqc_destroy": (None, [_vp]),
     "sdr_iqc_reset": (_i32, [_vp]),

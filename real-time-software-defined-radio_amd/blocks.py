@@ -28,6 +28,7 @@ from . import design
 from . import iqbalance
 from . import rowmeter
 from . import sosfilter
+from . import truepeak
 from ._lib import RX_FILTERS, RX_OUTPUTS, SDR_IQ_F32, SDR_IQ_U8, SDR_RX_AUDIO, SDR_RX_RDS, SDR_RX_STEREO, check, f64p
 from .dsp import _taps
 
@@ -516,6 +517,12 @@ class Receiver(_Timed, _Handle):
         meter.report()."""
         kw.setdefault("ctx", self.ctx)
         return LoudnessMeter(self.S, channels=len(self.loudness_rows()), **kw)
+
+    def true_peak_meter(self, **kw) -> "TruePeakMeter":
+        """A TruePeakMeter sized to this receiver's 48 kHz audio rows, the channels of loudness_meter():
+        feed it with meter.process_rx(receiver) after a block and read meter.report()."""
+        kw.setdefault("ctx", self.ctx)
+        return TruePeakMeter(self.S, channels=len(self.loudness_rows()), **kw)
 
     def loudness_rows(self) -> tuple:
         """The outputs a loudness meter of this receiver reads (LoudnessMeter.process_rx's default)."""
@@ -1817,6 +1824,10 @@ class LoudnessMeter(_Timed, _LazyHandle):
         """rtsdr.loudness_report of the kept segments (a segment must be 100 ms of 48 kHz: 4800)."""
         return sosfilter.loudness_report(self.segments()[1], self.segment)
 
+    def loudness_range(self) -> "truepeak.LoudnessRange":
+        """rtsdr.loudness_range (EBU Tech 3342) of the kept segments (a segment must be 100 ms of 48 kHz: 4800)."""
+        return truepeak.loudness_range(self.segments()[1], self.segment)
+
     def state_ptr(self):
         """(ring pointer, open pointer): the device arrays float64 [nstreams][channels][cap] (segment g
         at g % cap) and [nstreams][channels] (sdr_loud_state_dev)."""
@@ -1824,6 +1835,110 @@ class LoudnessMeter(_Timed, _LazyHandle):
 
     def reset(self):
         """Zero the filter states, the segments and the stream position (async)."""
+        self._do("reset")
+
+
+class _TpeakParamsC(ctypes.Structure):                           # include/sdr.h sdr_tpeak_params
+    _fields_ = [("up", ctypes.c_int), ("taps", ctypes.c_int), ("h", ctypes.c_void_p), ("segment", ctypes.c_int64), ("cap", ctypes.c_int)]
+
+
+class _TpeakRecordC(ctypes.Structure):                           # include/sdr.h sdr_tpeak_record
+    _fields_ = [(k, ctypes.c_int64 if truepeak.field_dtype(k) is np.int64 else ctypes.c_double) for k in truepeak.FIELDS]
+
+
+class TruePeakMeter(_Timed, _LazyHandle):
+    """The true peak of `nstreams` audio streams of 1 or 2 channels on the GPU (sdr_tpeak,
+    csrc/tpeak.hip), read from a Receiver's 48 kHz audio rows where it left them: per input sample
+    the `up` values of a polyphase interpolator `taps` ([up, taps] float32; None: the 4 x 12 table
+    of ITU-R BS.1770-4 annex 2, design.true_peak_fir) as float64 chains in registers, of which only
+    maxima are kept -- per completed segment of `segment` samples (4800: 100 ms) of stream position
+    the true peak and the sample peak, the latest `cap` of them per stream and channel, and a record
+    of the call and the totals.  Two launches per call, nothing returns to the host until records(),
+    segments() or report() is asked.  The rule is rtsdr.TruePeakModel, which the device equals bit
+    for bit; report() is rtsdr.true_peak_report in dBTP relative to `reference`, the row amplitude
+    of PCM full scale (the output stage writes int16(x * 16384), so 2.0).  The arguments are checked
+    before a context exists."""
+
+    MAX_N = sosfilter.MAX_N
+    _prefix = "sdr_tpeak"
+    _STAGES = ("reduce", "fold")                                  # stage_ms: the last call's two launches
+
+    def __init__(self, nstreams: int, channels: int = 2, segment: int = 4800, cap: int = 4096, taps=None, reference: float = 2.0, ctx=None):
+        self.nstreams, self.channels, self.segment, self.cap, self.taps = truepeak.check_params(nstreams, channels, segment, cap, taps)
+        self.reference = float(reference)
+        if not (np.isfinite(self.reference) and self.reference > 0):
+            raise ValueError(f"reference={reference} is not finite and positive")
+        self._ctx = ctx
+
+    def _create_args(self):
+        up, taps = self.taps.shape
+        return self.nstreams, self.channels, ctypes.byref(_TpeakParamsC(up, taps, self.taps.ctypes.data, self.segment, self.cap))
+
+    def process_dev(self, ch0_ptr: int, ch1_ptr: int, stride: int, n: int):
+        """n samples per row of each channel at device pointers ch0_ptr and ch1_ptr (0 / None with one
+        channel), rows stride floats apart, any 4-byte alignment; async on the context stream."""
+        p0, p1, stride, n = int(ch0_ptr or 0), int(ch1_ptr or 0), int(stride), int(n)
+        if not p0 or bool(p1) != (self.channels == 2):
+            raise ValueError(f"{self.channels} channel(s): ch0_ptr must be given, ch1_ptr with two channels only")
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError(f"n={n} outside [1, 2^31 - 1]")
+        if stride < n:
+            raise ValueError(f"stride={stride} < n={n}")
+        if p0 % 4 or p1 % 4:
+            raise ValueError("the row pointers must be aligned to 4 B")
+        self._do("process_dev", p0, p1 or None, stride, n)
+
+    def process_rx(self, receiver: "Receiver", names=None):
+        """The receiver's latest rows of the outputs `names`, one per channel, read in place (None:
+        receiver.loudness_rows()).  Call it before the receiver's next process_dev, which keeps the
+        rows until this call has read them."""
+        if receiver.S != self.nstreams:
+            raise ValueError(f"the receiver has {receiver.S} streams, the meter {self.nstreams}")
+        names = receiver.loudness_rows() if names is None else tuple(names)
+        if len(names) != self.channels:
+            raise ValueError(f"{len(names)} outputs for {self.channels} channel(s)")
+        rows = [receiver.output_ptr(k) for k in names]
+        if any(r[1:] != rows[0][1:] for r in rows):
+            raise ValueError("the channels' rows differ in stride or length")
+        self.process_dev(rows[0][0], rows[1][0] if self.channels == 2 else None, rows[0][1], rows[0][2])
+
+    def run(self, rows_host):
+        """A list of `channels` arrays (nstreams, n) from the host; synchronous (sdr_tpeak_run)."""
+        if len(rows_host) != self.channels:
+            raise ValueError(f"{len(rows_host)} row sets for {self.channels} channel(s)")
+        xs = [np.ascontiguousarray(sosfilter.as_rows(r, self.nstreams)) for r in rows_host]
+        if any(x.shape != xs[0].shape for x in xs):
+            raise ValueError("the channels' rows differ in length")
+        self._do("run", xs[0].ctypes.data, xs[1].ctypes.data if self.channels == 2 else None, xs[0].shape[1], xs[0].shape[1])
+
+    def records(self) -> "truepeak.TruePeakRecord":
+        """The state after the latest call, every field [nstreams, channels] (sdr_tpeak_records; synchronises)."""
+        raw = (_TpeakRecordC * (self.nstreams * self.channels))()
+        self._do("records", ctypes.byref(raw))
+        return truepeak.TruePeakRecord(*(np.array([getattr(r, k) for r in raw], dtype=truepeak.field_dtype(k)).reshape(self.nstreams, self.channels)
+                                         for k in truepeak.FIELDS))
+
+    def segments(self):
+        """(first, peaks, sample_peaks): float64 [nstreams, channels, count] each, the latest min(cap,
+        completed) segments' true and sample peaks in order, and the stream index of the first
+        (sdr_tpeak_segments; synchronises)."""
+        pk, sp = (np.empty((self.nstreams, self.channels, self.cap)) for _ in range(2))
+        first, count = ctypes.c_int64(), ctypes.c_int64()
+        self._do("segments", pk.ctypes.data, sp.ctypes.data, ctypes.byref(first), ctypes.byref(count))
+        return first.value, np.ascontiguousarray(pk[:, :, :count.value]), np.ascontiguousarray(sp[:, :, :count.value])
+
+    def report(self) -> "truepeak.TruePeakReport":
+        """rtsdr.true_peak_report of the kept segments and the records, relative to `reference`."""
+        _, pk, sp = self.segments()
+        return truepeak.true_peak_report(pk, sp, self.records(), self.reference)
+
+    def state_ptr(self):
+        """(true-peak ring, sample-peak ring, records): the device arrays float64 [nstreams][channels][cap]
+        (segment g at g % cap) twice and struct sdr_tpeak_record [nstreams][channels] (sdr_tpeak_state_dev)."""
+        return self._ptr_out("state_dev", 3)
+
+    def reset(self):
+        """Zero the history, the segments, the records and the stream position (async)."""
         self._do("reset")
 
 

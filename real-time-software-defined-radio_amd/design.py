@@ -202,6 +202,18 @@ def k_weighting_sos(fs: float = 48e3) -> np.ndarray:
                      [1.0, -2.0, 1.0, 1.0, -1.99004745483398, 0.99007225036621]])
 
 
+TRUE_PEAK_FIR_8192 = ((14, 90, -161, 272, -487, 1125, 7964, -838, 390, -218, 122, -68),
+                      (-239, 240, -424, 730, -1364, 3810, 6388, -1641, 832, -477, 271, -155))
+
+
+def true_peak_fir() -> np.ndarray:
+    """The 48-tap, 4-phase interpolator of ITU-R BS.1770-4 annex 2 (x4 oversampling of 48 kHz rows) as
+    float32 [4, 12]: integers / 8192, each exact in float32; phases 2 and 3 are phases 1 and 0
+    reversed.  Phase p, tap k weighs the sample k in front of the newest."""
+    a = np.array(TRUE_PEAK_FIR_8192, dtype=np.float64)
+    return np.ascontiguousarray(np.concatenate([a, a[::-1, ::-1]]) / 8192.0, dtype=np.float32)
+
+
 def pilot_notch_sos(fs: float = 48e3, f0: float = PILOT_FREQ, q: float = 30.0) -> np.ndarray:
     """A notch at the 19 kHz pilot for the audio rows: signal.tf2sos(*signal.iirnotch(f0, q, fs)),
     one section, -3 dB width f0 / q."""
